@@ -9,6 +9,17 @@ per-GPU partials are exchanged with one RCCL all-gather and combined in rank
 order.  Those statistics give mean, max and min (C3's three methods).
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3]
+                       [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the JSON line
+(``value``, ``ms_per_step``, the roofline figures of the timed kernel).
+``--dump-outputs DIR`` also writes what the last timed step computed (the
+combined partial a caller of the path receives) as ``DIR/sum.npy``,
+``count.npy``, ``min.npy`` and ``max.npy`` (float64); the inputs are seeded,
+so two builds run with the same arguments can be compared output for output.
+``--full`` adds everything else: the torch and single-rank-combine checks of
+the result, the CPU baseline and oracle check, the host- and file-inclusive
+legs and the ``--extra`` configs.
 
 Multi-GPU: either ``python -m torch.distributed.run --nproc-per-node N
 bench.py --gpus N`` (WORLD_SIZE/RANK/LOCAL_RANK from the launcher), or plain
@@ -17,11 +28,11 @@ process starts N rank processes itself (before anything touches the GPU) and
 exits with their status.  It never runs fewer ranks than ``--gpus`` asks for.
 
 The JSON line's headline (``value``) is C3 at the chosen scaling (weak by
-default: each GPU adds a 1024^3 slab).  ``extra`` adds the two 8-GPU configs
-of BASELINE.json measured at the same N, both strong scaling (one fixed
-variable split over the ranks): C4 2048^3 f32 128^3 shuffled + masked
-(4096 chunks, 4096/N per rank) and C5 4096x2048x1024 f64 32^3 hyperslab
-masked mean (262,144 chunks).
+default: each GPU adds a 1024^3 slab).  With ``--full``, ``extra`` adds the
+two 8-GPU configs of BASELINE.json measured at the same N, both strong
+scaling (one fixed variable split over the ranks): C4 2048^3 f32 128^3
+shuffled + masked (4096 chunks, 4096/N per rank) and C5 4096x2048x1024 f64
+32^3 hyperslab masked mean (262,144 chunks).
 """
 from __future__ import annotations
 
@@ -74,16 +85,23 @@ def parse(argv=None):
     p.add_argument("--warmup", type=int, default=5)
     p.add_argument("--config", default="c3", choices=sorted(CONFIGS))
     p.add_argument("--tile-bytes", type=int, default=0)
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline does not need: the result checks (torch ops, "
+                        "single-rank combine), the CPU baseline and oracle check, the host- and "
+                        "file-inclusive legs and the --extra configs (all skipped without it)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write the last timed step's result (sum, count, "
+                        "min, max of the headline config) as DIR/<name>.npy, float64")
     p.add_argument("--scaling", default="weak", choices=("weak", "strong"),
                    help="weak: each GPU adds its own slab of the variable (dim 0); "
                         "strong: one variable of the config's shape split across GPUs")
     p.add_argument("--extra", default="c4,c5,c3_slab,c3_stride",
-                   help="comma list of configs also measured at this N with strong scaling "
-                        "(reported under 'extra'; 'none' to skip); c3_slab / c3_stride: the "
+                   help="with --full: comma list of configs also measured at this N with strong "
+                        "scaling (reported under 'extra'; 'none' to skip); c3_slab / c3_stride: the "
                         "reference's query shapes through Active on C3 (N=1 only)")
     p.add_argument("--extra-steps", type=int, default=20)
     p.add_argument("--cpu-chunks", type=int, default=4096,
-                   help="chunks in the CPU-baseline sample (0 = skip)")
+                   help="with --full: chunks in the CPU-baseline sample (0 = skip)")
     p.add_argument("--cpu-threads", type=int, default=30)
     p.add_argument("--force-dist", action="store_true",
                    help="rehearsal: run the RCCL branch (init, all-gather, device combine) "
@@ -93,9 +111,9 @@ def parse(argv=None):
                         "exchange staged through host memory, ranks may share a GPU (rehearsal "
                         "of --gpus N on a smaller box)")
     p.add_argument("--host-inclusive", type=int, default=1,
-                   help="also time pinned host -> H2D -> reduce -> D2H (rank 0, N=1)")
+                   help="with --full: also time pinned host -> H2D -> reduce -> D2H (rank 0, N=1)")
     p.add_argument("--file-inclusive", type=int, default=1,
-                   help="also time file (page cache) -> native pread ring -> H2D -> reduce -> scalar "
+                   help="with --full: also time file (page cache) -> native pread ring -> H2D -> reduce -> scalar "
                         "(rank 0, N=1)")
     p.add_argument("--traffic-file", default=os.path.join(ROOT, "profiles", "traffic.json"))
     p.add_argument("--selftest-launch", action="store_true",
@@ -113,7 +131,12 @@ def parse(argv=None):
     p.add_argument("--dist-timeout", type=float, default=300.0,
                    help="seconds a collective may wait before torch.distributed aborts it "
                         "(init_process_group timeout)")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    if not args.full:   # a plain run measures the headline only
+        args.extra, args.cpu_chunks, args.host_inclusive, args.file_inclusive = "none", 0, 0, 0
+    return args
 
 
 # ---------------------------------------------------------------------------
@@ -478,10 +501,11 @@ def _same(a, b, rel=1e-6):
 
 
 def run_config(env, name, scaling, steps, warmup, args, full_check=False):
-    """Build one config's data and plan on this rank, time ``steps`` steps
-    (barrier + synchronize on both sides, max over ranks), then self-check
-    the sharded result against the single-rank combine of all chunk
-    partials.  Returns the per-config report (on every rank)."""
+    """Build one config's data and plan on this rank and time ``steps`` steps
+    (barrier + synchronize on both sides, max over ranks).  With ``--full``
+    then self-check the sharded result against the single-rank combine of
+    all chunk partials.  Returns the per-config report, the achieved GB/s
+    and the last timed step's combined partial (on every rank)."""
     torch, dist, ctx, dev, stream = env["torch"], env["dist"], env["ctx"], env["dev"], env["stream"]
     rank, world, use_dist = env["rank"], env["world"], env["use_dist"]
     coll_dev = env["coll_dev"]   # where collective tensors live (the GPU for RCCL, the host for gloo)
@@ -517,7 +541,7 @@ def run_config(env, name, scaling, steps, warmup, args, full_check=False):
     bytes_per_launch = int(counts.sum()) * dt.itemsize
 
     check = None
-    if full_check and not cfg["shuffle"] and sels is None:
+    if full_check and args.full and not cfg["shuffle"] and sels is None:
         # independent device check of count/sum/min/max with plain torch ops
         tdt = torch.float32 if dt.itemsize == 4 else torch.float64
         v = data[: bytes_per_launch].view(tdt)
@@ -579,26 +603,35 @@ def run_config(env, name, scaling, steps, warmup, args, full_check=False):
     elapsed_max = float(per[:, 0].max())
     total_bytes, total_chunks = float(per[:, 3].sum()), float(per[:, 4].sum())
 
-    # result + self-check: one more sharded step, then the single-rank
+    # what the last timed step left: this rank's total, or the exchanged and
+    # combined one (--dump-outputs writes it; a plain run reports it)
+    if use_dist:
+        timed_out = np.frombuffer(final.cpu().numpy().tobytes(), dtype=engine.partial_dtype(dt))[0]
+    else:
+        timed_out = plan.read_total(stream)[0]
+    result = _partials_dict(timed_out)
+
+    # --full: result + self-check: one more sharded step, then the single-rank
     # combine (pyas_combine_partials, variable-dtype rounding) over every
     # chunk partial of every rank in global chunk order must give the same
     # count/min/max and the sum within 1e-6
-    plan.launch(stream, chunk_partials=True)
-    local_total = _partials_dict(plan.read_total(stream)[0])
-    if use_dist:
-        reduce_sharded(torch, plan, ctx, stream, final, launch=False)
-        torch.cuda.synchronize()
-        result = _partials_dict(np.frombuffer(final.cpu().numpy().tobytes(),
-                                              dtype=engine.partial_dtype(dt))[0])
-    else:
-        result = local_total
-    cparts = plan.read_chunk_partials(stream)
-    if use_dist:   # every rank's chunk partials (32 B each), as tensors
-        cat = b"".join(all_gather_bytes(torch, cparts.tobytes(), coll_dev))
-    else:
-        cat = cparts.tobytes()
     selfcheck = None
-    if rank == 0:
+    if args.full:
+        plan.launch(stream, chunk_partials=True)
+        local_total = _partials_dict(plan.read_total(stream)[0])
+        if use_dist:
+            reduce_sharded(torch, plan, ctx, stream, final, launch=False)
+            torch.cuda.synchronize()
+            result = _partials_dict(np.frombuffer(final.cpu().numpy().tobytes(),
+                                                  dtype=engine.partial_dtype(dt))[0])
+        else:
+            result = local_total
+        cparts = plan.read_chunk_partials(stream)
+        if use_dist:   # every rank's chunk partials (32 B each), as tensors
+            cat = b"".join(all_gather_bytes(torch, cparts.tobytes(), coll_dev))
+        else:
+            cat = cparts.tobytes()
+    if args.full and rank == 0:
         n_tot = len(cat) // _lib.PARTIAL_NBYTES
         inp = torch.frombuffer(bytearray(cat), dtype=torch.uint8).to(dev)
         one = torch.zeros(_lib.PARTIAL_NBYTES, dtype=torch.uint8, device=dev)
@@ -637,7 +670,15 @@ def run_config(env, name, scaling, steps, warmup, args, full_check=False):
         "frac_min_rank": round(float((per[:, 3] / (per[:, 1] * 1e-3) / 1e9).min()) / HBM_PEAK_GBS, 4),
         "result": result, "selfcheck": selfcheck, "check": check,
     }
-    return rep, achieved
+    return rep, achieved, timed_out
+
+
+def dump_outputs(path, partial):
+    """Write the combined partial of the last timed step as
+    ``path/<field>.npy`` (sum, count, min, max), one float64 value each."""
+    os.makedirs(path, exist_ok=True)
+    for k in ("sum", "count", "min", "max"):
+        np.save(os.path.join(path, f"{k}.npy"), np.array([partial[k]], dtype=np.float64))
 
 
 # The reference's own query shapes at C3 size (tests/unit/test_active_axis.py:30-39:
@@ -809,8 +850,10 @@ def main():
 
     cfg = CONFIGS[args.config]
     dt = np.dtype(cfg["dtype"])
-    head, achieved = run_config(env, args.config, args.scaling, args.steps, args.warmup, args,
-                                full_check=True)
+    head, achieved, timed_out = run_config(env, args.config, args.scaling, args.steps, args.warmup,
+                                           args, full_check=True)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, timed_out)
 
     traffic = None
     try:
@@ -874,7 +917,7 @@ def main():
             continue
         if name not in CONFIGS:
             raise SystemExit(f"bench.py: unknown --extra config {name!r}")
-        rep, _ = run_config(env, name, "strong", args.extra_steps, args.warmup, args)
+        rep, _, _ = run_config(env, name, "strong", args.extra_steps, args.warmup, args)
         rep.pop("check", None)
         extra[f"{name}_strong"] = rep
 

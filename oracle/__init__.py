@@ -1,7 +1,7 @@
 """CPU oracle for the chunk-reduction hot path — TEST INFRASTRUCTURE ONLY.
 
 Nothing in ``pyactivestorage_amd`` imports this package. Only ``tests/``,
-``__graft_entry__.smoke()`` and the ``cpu_baseline`` leg of ``bench.py`` may
+``__graft_entry__.smoke()`` and the ``cpu_baseline`` leg of ``bench.py --full`` may
 use it, and only as the checker / the timed CPU baseline, never as the thing
 that is measured or shipped.
 

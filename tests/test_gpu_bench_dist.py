@@ -19,8 +19,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.parametrize("world", [2, 3])
 def test_bench_ranks_gloo_share_one_gpu(gpu, world):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--dist-backend", "gloo",
-           "--config", "t3", "--extra", "t4,t5", "--steps", "3", "--warmup", "1", "--extra-steps", "3",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(world),
+           "--dist-backend", "gloo", "--config", "t3", "--extra", "t4,t5", "--steps", "3", "--warmup", "1", "--extra-steps", "3",
            "--cpu-chunks", "0", "--host-inclusive", "0", "--file-inclusive", "0"]
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)

@@ -1,4 +1,4 @@
-"""Print the c3_slab / c3_stride query lines of a bench.py JSON output."""
+"""Print the c3_slab / c3_stride query lines of a ``bench.py --full`` JSON output."""
 import json
 import sys
 
