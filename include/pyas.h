@@ -521,6 +521,39 @@ int pyas_tie_keys_reset(pyas_ctx *ctx, uint64_t *keys, int64_t n_out, void *stre
 int pyas_tie_finalize(pyas_ctx *ctx, int32_t dtype, const uint64_t *keys, int64_t n_out, int32_t n_sets,
                       int64_t lr, uint32_t which, pyas_partial *final_, void *stream);
 
+/* ---- second moments (Active.var / Active.std) ------------------------------
+ * Partial record of a masked variance over a set of elements (32 bytes):
+ * count unmasked elements; mean of them; m2 = sum (x - mean)^2  (all in f64).
+ * count == 0 is neutral (mean, m2 ignored; written as 0).  Integer values
+ * convert to f64 as astype(float64) does.  One pass: each lane keeps a shift K
+ * (its first unmasked value) with sum (x-K) and sum (x-K)^2 in f64; lanes,
+ * waves, tiles and chunks merge in a fixed order with Chan's formula
+ *   d = mean_b - mean_a;  mean = mean_a + d n_b/n;  m2 = m2_a + m2_b + d^2 n_a n_b/n
+ * (a side with count 0 is skipped), so results are bit-identical from run to
+ * run.  An unmasked NaN gives NaN mean and m2, an unmasked +-inf a NaN m2.
+ * The mean travels as one f64, so a merge of records whose means differ by
+ * about sigma costs about 2^-53 |mean| / sigma relative in m2. */
+typedef struct { int64_t count; double mean; double m2; uint64_t reserved; } pyas_moments;
+
+/* pyas_reduce_axes for moments: out[out_offsets[c] + o] receives the record
+ * of output o (C order over the kept selected dims) of chunk c.  With every
+ * dim in axes_mask each chunk yields one record (at out[out_offsets[c]], or
+ * out[c] when out_offsets is NULL), streamed with 16-byte loads where the
+ * chunk is whole or its selection one contiguous run.  Like pyas_reduce_axes
+ * the selection table is trusted (the host checks it: PYAS_EINDEX). */
+int pyas_moments_axes(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask,
+                      uint32_t axes_mask, const int64_t *out_offsets, pyas_moments *out,
+                      void *stream);
+/* pyas_combine_segments for moments records (same order: index order inside
+ * a segment); index NULL: the identity (segment s folds in[seg[s] .. seg[s+1])). */
+int pyas_moments_combine_segments(pyas_ctx *ctx, const pyas_moments *in, const int64_t *index,
+                                  const int64_t *seg_offsets, int64_t n_segments,
+                                  pyas_moments *out, void *stream);
+/* pyas_combine_grid for moments records (same order: C order over the reduced
+ * dims' chunk coordinates). */
+int pyas_moments_combine_grid(pyas_ctx *ctx, const pyas_moments *in, const pyas_grid *grid,
+                              pyas_moments *out, void *stream);
+
 /* Result formatting on the device: the last step of Active._from_storage
  * (active.py:591-630) applied to n combined partials (device), so that only
  * the result's values and mask cross PCIe (9-16 bytes per output instead of

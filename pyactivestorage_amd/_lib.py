@@ -37,6 +37,12 @@ class Partial(ctypes.Structure):
     _fields_ = [("sum", Scalar), ("count", ctypes.c_int64), ("min", Scalar), ("max", Scalar)]
 
 
+class Moments(ctypes.Structure):
+    """pyas_moments: count, mean and m2 = sum (x - mean)^2 of a set of elements."""
+    _fields_ = [("count", ctypes.c_int64), ("mean", ctypes.c_double), ("m2", ctypes.c_double),
+                ("reserved", ctypes.c_uint64)]
+
+
 class Mask(ctypes.Structure):
     _fields_ = [
         ("flags", ctypes.c_uint32),
@@ -143,6 +149,8 @@ def combine_rec(rec: int) -> int:
 
 PARTIAL_NBYTES = ctypes.sizeof(Partial)
 assert PARTIAL_NBYTES == 32
+MOMENTS_NBYTES = ctypes.sizeof(Moments)
+assert MOMENTS_NBYTES == 32
 
 _vp = ctypes.c_void_p
 _i32 = ctypes.c_int32
@@ -196,6 +204,9 @@ SIGNATURES = {
     "pyas_combine_grid": [_vp, _i32, _vp, ctypes.POINTER(Grid), _u32, _vp, _vp],
     "pyas_reduce_axes_grid": [_vp, ctypes.POINTER(Batch), ctypes.POINTER(Mask), ctypes.POINTER(Grid), _u32,
                               _vp, _vp],
+    "pyas_moments_axes": [_vp, ctypes.POINTER(Batch), ctypes.POINTER(Mask), _u32, _vp, _vp, _vp],
+    "pyas_moments_combine_segments": [_vp, _vp, _vp, _vp, _i64, _vp, _vp],
+    "pyas_moments_combine_grid": [_vp, _vp, ctypes.POINTER(Grid), _vp, _vp],
     "pyas_format_partials": [_vp, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _vp],
     "pyas_unshuffle": [_vp, _vp, _vp, _i64, _i32, _vp],
     "pyas_unshuffle_chunks": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp],

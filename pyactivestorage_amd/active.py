@@ -1,7 +1,7 @@
 """Batched ``Active`` front end: one device launch chain per query.
 
 Mirrors ``activestorage/active.py``'s user API (``Active(path, ncvar)``,
-``Active.method``, ``.mean()/.min()/.max(axis)``, ``.components``,
+``Active.method``, ``.mean()/.min()/.max()/.sum(axis)``, ``.components``,
 ``active[index]``, ``active.py:162-427``).  The dataset is a netCDF4/HDF5
 path, whose metadata and chunk index :mod:`.hdf5` reads (pyfive's part in
 the reference), or a :class:`~pyactivestorage_amd.variable.ChunkedVariable`.
@@ -24,6 +24,10 @@ the reference), or a :class:`~pyactivestorage_amd.variable.ChunkedVariable`.
    contiguous share of the chunks, then one all-gather and a rank-order
    device combine (row e);
 5. host: format the combined partials exactly like ``active.py:591-630``.
+
+Beyond the reference: ``.var(axis, ddof)`` / ``.std(axis, ddof)``, one pass of
+count / mean / m2 records (``pyas_moments_axes``) merged with Chan's formula
+in the order the sums are combined in (``_reduce_moments``).
 """
 from __future__ import annotations
 
@@ -35,7 +39,7 @@ import warnings
 
 import numpy as np
 
-from . import _lib, engine, selection, zerosign
+from . import _lib, engine, moments, selection, zerosign
 from .batch import ReductionPlan, _all_full
 from .device import DeviceBuffer, get_context
 from .dtypes import native, sum_dtype
@@ -47,6 +51,7 @@ from .storage import _decompress, _shuffle_sizes
 from .variable import ChunkedVariable, decode_filters, get_missing_attributes
 
 _ALIGN = 256
+_MOMENTS_SEG = 64   # records a thread folds per level of a full var / std reduction
 _RESIDENT_LOCK = threading.Lock()
 _RESIDENT_CV = threading.Condition(_RESIDENT_LOCK)   # slot state changes
 _EMPTY, _LOADING, _LOADED = 0, 1, 2
@@ -273,7 +278,8 @@ class Active:
 
     def __new__(cls, *args, **kwargs):
         inst = super().__new__(cls)
-        inst._methods = {"min": np.ma.min, "max": np.ma.max, "sum": np.ma.sum, "mean": np.ma.sum}
+        inst._methods = {"min": np.ma.min, "max": np.ma.max, "sum": np.ma.sum, "mean": np.ma.sum,
+                         "var": np.ma.var, "std": np.ma.std}
         return inst
 
     def __init__(self, dataset, ncvar=None, axis=None, interface_type=None, max_threads: int = 30,
@@ -312,6 +318,7 @@ class Active:
         self._axis = axis
         self._components = False
         self._method = None
+        self._ddof = 0                  # var / std: the divisor is count - ddof
         self._max_threads = int(max_threads)
         self.device = device
         # f3: zlib chunks inflate on the GPU (True), on the host reader threads
@@ -350,6 +357,7 @@ class Active:
         if value is not None and value not in self._methods:
             raise ValueError(f"Bad 'method': {value}. Choose from min/max/mean/sum.")
         self._method = value
+        self._ddof = 0
 
     def mean(self, axis=None):
         self._method = "mean"
@@ -369,6 +377,31 @@ class Active:
             self._axis = axis
         return self
 
+    def sum(self, axis=None):
+        self._method = "sum"
+        if axis is not None:
+            self._axis = axis
+        return self
+
+    def var(self, axis=None, ddof=0):
+        """Variance of the unmasked elements, ``m2 / (count - ddof)`` in
+        float64 (``np.ma.var`` of the float64 selection), masked where
+        ``count - ddof <= 0``.  One pass on the device (pyas_moments_axes)."""
+        return self._set_moments("var", axis, ddof)
+
+    def std(self, axis=None, ddof=0):
+        """Standard deviation: the square root of :meth:`var`."""
+        return self._set_moments("std", axis, ddof)
+
+    def _set_moments(self, method, axis, ddof):
+        if isinstance(ddof, (bool, np.bool_)) or not isinstance(ddof, (int, np.integer)) or ddof < 0:
+            raise ValueError(f"ddof must be a non-negative int. Got {ddof!r}")
+        self._method = method
+        self._ddof = int(ddof)
+        if axis is not None:
+            self._axis = axis
+        return self
+
     # -- query -------------------------------------------------------------
     def __getitem__(self, index):
         self.missing = get_missing_attributes(self.ds.attrs)
@@ -384,12 +417,16 @@ class Active:
 
     def _get_selection(self, index):
         ds = self.ds
+        second = self._method in ("var", "std")
+        if second and self.group is not None:
+            raise NotImplementedError("var/std with group=…: second moments are reduced on one GPU only")
         if self._axis is None:
             self._axis = tuple(range(ds.ndim))
         elif isinstance(self._axis, int):
             self._axis = (self._axis,)
         cache_key = None
-        if self.resident and self.group is None and self._method is not None:
+        # (var / std bypass the plan cache: its plans replay pyas_partial launches)
+        if self.resident and self.group is None and self._method is not None and not second:
             ikey = _index_key(index)
             if ikey is not None:
                 cache_key = (ikey, self._norm_axes(), _missing_key(self.missing))
@@ -407,6 +444,8 @@ class Active:
             if d.kind == "int":
                 raise IndexError("Can't do an active reduction when the index for "
                                  f"axis {i!r} drops the axis.")
+        if second:
+            return self._reduce_moments(indexer, compressor, filters, self._norm_axes())
         return self._reduce(indexer, compressor, filters, self._norm_axes(), cache_key)
 
     def _norm_axes(self):
@@ -775,6 +814,124 @@ class Active:
                                  set(axes))
             final = self._exchange(final, keys[0], lr)
         return self._format(final.reshape(final_shape), final_shape)
+
+    # -- var / std ------------------------------------------------------------
+    def _reduce_moments(self, indexer, compressor, filters, axes):
+        """var / std: per-chunk count / mean / m2 records (pyas_moments_axes)
+        merged with Chan's formula in the order the sums are combined in: a
+        full reduction in chunk order, a box query over the chunk layers of
+        each output (pyas_moments_combine_grid), anything else over host-built
+        segments (pyas_moments_combine_segments)."""
+        ds = self.ds
+        final_shape = tuple(1 if i in axes else n for i, n in enumerate(indexer.shape))
+        n_final = int(np.prod(final_shape))
+        final = np.zeros(n_final, dtype=engine.moments_dtype)
+        box = self._box_plan(indexer)
+        dims = None
+        if box is not None:
+            dims, coords, table, pool = box
+            n = len(coords)
+        else:
+            chunk_list = list(indexer)
+            n = len(chunk_list)
+        if n == 0 or n_final == 0:
+            return self._format_moments(final.reshape(final_shape))
+        if box is not None:
+            ctx, st, buf, offsets, fused = self._ingest(coords, compressor, filters)
+            full = _all_full(table, ds.chunks)
+            plan = ReductionPlan(ctx, ds.dtype, ds.chunks, buf.ptr, offsets, shuffle=fused,
+                                 sel_table=None if full else table, index_pool=None if full else pool,
+                                 missing=self.missing, stream=st)
+        else:
+            ctx, st, buf, offsets, fused = self._ingest([c for c, _ in chunk_list], compressor, filters)
+            sels = [self._chunk_sel(projs) for _, projs in chunk_list]
+            plan = ReductionPlan(ctx, ds.dtype, ds.chunks, buf.ptr, offsets, shuffle=fused, selections=sels,
+                                 missing=self.missing, stream=st)
+        axes_mask = 0
+        for a in axes:
+            axes_mask |= 1 << a
+        nb = _lib.MOMENTS_NBYTES
+        fin = DeviceBuffer(ctx, n_final * nb)
+        keep = [buf]
+        if len(axes) == ds.ndim:
+            # one record per chunk, folded in chunk order: groups of _MOMENTS_SEG
+            # consecutive records per thread, level after level (a fixed
+            # function of the chunk count alone)
+            # (one allocation: every level's records, then every level's segment bounds)
+            levels, m = [], n
+            while True:
+                n_seg = -(-m // _MOMENTS_SEG)
+                levels.append((n_seg, np.minimum(np.arange(n_seg + 1, dtype=np.int64) * _MOMENTS_SEG, m)))
+                if n_seg == 1:
+                    break
+                m = n_seg
+            segs = np.concatenate([seg for _, seg in levels])
+            n_rec = n + sum(n_seg for n_seg, _ in levels[:-1])
+            work = DeviceBuffer(ctx, n_rec * nb + segs.nbytes)
+            keep.append(work)
+            cur, sptr = work.ptr, work.ptr + n_rec * nb
+            ctx.h2d(sptr, segs, st)
+            engine.moments_axes(ctx, plan.batch, plan.mask_up.struct, axes_mask, None, cur, st)
+            nxt = cur + n * nb
+            for n_seg, seg in levels:
+                dst = fin.ptr if n_seg == 1 else nxt
+                engine.moments_combine_segments(ctx, cur, None, sptr, n_seg, dst, st)
+                cur, nxt, sptr = dst, dst + n_seg * nb, sptr + seg.nbytes
+        elif dims is not None:
+            out_off, tables = self._grid_from_dims(dims, axes, final_shape)
+            obuf = DeviceBuffer(ctx, out_off.nbytes)
+            ctx.h2d(obuf.ptr, out_off, st)
+            tbuf = DeviceBuffer(ctx, max(tables["blob"].nbytes, 16))
+            ctx.h2d(tbuf.ptr, tables["blob"], st)
+            g = _lib.Grid()
+            g.ndim = ds.ndim
+            g.axes_mask = axes_mask
+            for d in range(ds.ndim):
+                g.n_coords[d] = tables["n_coords"][d]
+                g.out_extent[d] = final_shape[d] if d not in axes else 1
+                if d not in axes:
+                    g.pos_coord[d] = tbuf.ptr + 4 * tables["pos_coord"][d]
+                    g.pos_local[d] = tbuf.ptr + 4 * tables["pos_local"][d]
+                    g.coord_count[d] = tbuf.ptr + 4 * tables["coord_count"][d]
+            g.chunk_out_offsets = obuf.ptr
+            parts = DeviceBuffer(ctx, max(int(tables["n_parts"]), 1) * nb)
+            engine.moments_axes(ctx, plan.batch, plan.mask_up.struct, axes_mask, obuf.ptr, parts.ptr, st)
+            engine.moments_combine_grid(ctx, parts.ptr, g, fin.ptr, st)
+            keep += [obuf, tbuf, parts]
+        else:
+            sizes, fidx = [], []
+            for _, projs in chunk_list:
+                pos = [p.out_pos if i not in axes else np.zeros(1, dtype=np.int64) for i, p in enumerate(projs)]
+                grids = np.meshgrid(*pos, indexing="ij")
+                fidx.append(np.ravel_multi_index([x.reshape(-1) for x in grids], final_shape))
+                sizes.append(grids[0].size)
+            out_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+            f_all = np.concatenate(fidx)
+            order = np.argsort(f_all, kind="stable").astype(np.int64)
+            seg = np.searchsorted(f_all[order], np.arange(n_final + 1)).astype(np.int64)
+            meta = np.concatenate([out_off[:-1], order, seg])
+            mbuf = DeviceBuffer(ctx, meta.nbytes)
+            ctx.h2d(mbuf.ptr, meta, st)
+            parts = DeviceBuffer(ctx, max(int(out_off[-1]), 1) * nb)
+            engine.moments_axes(ctx, plan.batch, plan.mask_up.struct, axes_mask, mbuf.ptr, parts.ptr, st)
+            engine.moments_combine_segments(ctx, parts.ptr, mbuf.ptr + 8 * n, mbuf.ptr + 8 * (n + order.size),
+                                            n_final, fin.ptr, st)
+            keep += [mbuf, parts]
+        ctx.d2h(final, fin.ptr, st)
+        ctx.synchronize(st)
+        del keep
+        return self._format_moments(final.reshape(final_shape))
+
+    def _format_moments(self, parts):
+        """The float64 result of a var / std query from its combined records
+        (moments.finalize), or its components."""
+        if self._components:
+            empty = parts["count"] == 0
+            return {"mean": np.ma.MaskedArray(np.ascontiguousarray(parts["mean"]), mask=empty),
+                    "m2": np.ma.MaskedArray(np.ascontiguousarray(parts["m2"]), mask=empty),
+                    "n": np.ma.MaskedArray(np.ascontiguousarray(parts["count"]),
+                                           mask=np.zeros(parts.shape, dtype=bool))}
+        return moments.finalize(parts, self._ddof, std=self._method == "std")
 
     def _tie_which(self) -> int:
         """1 / 2 when the query's min / max of a float variable must give

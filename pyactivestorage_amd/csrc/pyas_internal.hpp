@@ -255,6 +255,25 @@ hipError_t launch_tie_finalize(int dtype, const uint64_t *keys, int64_t n_out, i
                                const TieRule &t, uint32_t which, pyas_partial *fin, hipStream_t st);
 hipError_t launch_format(int dtype, const pyas_partial *in, int64_t n, int32_t method, void *values,
                          uint8_t *mask, int64_t *counts, hipStream_t st);
+// second moments (pyas_moments.hip): count / mean / m2 records
+struct MomentsArgs {
+    ReduceArgs r;                     // r.out unused
+    uint32_t axes;                    // reduced dims
+    int64_t bpc;                      // workgroups per chunk (full: tiles per chunk)
+    const int64_t *out_offsets;       // NULL (full only): chunk c's record at out[c]
+    pyas_moments *out;
+    pyas_moments *tiles;              // full with bpc > 1: one record per workgroup
+    bool bswap, masked;
+    bool row;                         // innermost dim reduced: a wave per output
+};
+hipError_t launch_moments_full(int dtype, const MomentsArgs &a, bool shuf, int64_t grid, hipStream_t st);
+hipError_t launch_moments_axes(int dtype, const MomentsArgs &a, bool shuf, int64_t grid, hipStream_t st);
+hipError_t launch_moments_tiles(const pyas_moments *tiles, int64_t tpc, int64_t n_chunks,
+                                const int64_t *out_offsets, pyas_moments *out, hipStream_t st);
+hipError_t launch_moments_segments(const pyas_moments *in, const int64_t *index, const int64_t *seg,
+                                   int64_t n_seg, pyas_moments *out, hipStream_t st);
+hipError_t launch_moments_grid(const pyas_moments *in, const pyas_grid &g, int64_t n_out, int64_t n_layers,
+                               pyas_moments *out, hipStream_t st);
 // host ingest (pyas_ingest.hip): pread ring -> pinned slots -> H2D
 struct Ingest;
 Ingest *ingest_create(int device);

@@ -25,6 +25,10 @@ def partial_dtype(dt) -> np.dtype:
     return np.dtype([("sum", c), ("count", "<i8"), ("min", c), ("max", c)])
 
 
+# Host view of ``pyas_moments`` (every storage dtype: the record is f64)
+moments_dtype = np.dtype([("count", "<i8"), ("mean", "<f8"), ("m2", "<f8"), ("reserved", "<u8")])
+
+
 @dataclass
 class Layout:
     """What every chunk of one variable shares."""
@@ -209,6 +213,26 @@ def combine_grid(ctx: Context, dt, in_ptr, grid: _lib.Grid, out_ptr, round_to_va
     flags = (_lib.COMBINE_ROUND_TO_VAR if round_to_var else 0) | _lib.combine_rec(rec) | (int(zero_sign) << 8)
     _lib.check(ctx.lib.pyas_combine_grid(ctx.handle, dtype_code(dt), in_ptr, ctypes.byref(grid), flags,
                                          out_ptr, stream), "pyas_combine_grid")
+
+
+def moments_axes(ctx: Context, batch: _lib.Batch, mask: _lib.Mask, axes_mask: int, out_offsets_ptr, out_ptr,
+                 stream) -> None:
+    """pyas_moments_axes: count / mean / m2 records per chunk output (one per
+    chunk, at ``out[c]`` when ``out_offsets_ptr`` is None, with every dim in
+    ``axes_mask``)."""
+    _lib.check(ctx.lib.pyas_moments_axes(ctx.handle, ctypes.byref(batch), ctypes.byref(mask), int(axes_mask),
+                                         out_offsets_ptr, out_ptr, stream), "pyas_moments_axes")
+
+
+def moments_combine_segments(ctx: Context, in_ptr, index_ptr, seg_ptr, n_seg, out_ptr, stream) -> None:
+    """pyas_moments_combine_segments (``index_ptr`` None: the identity)."""
+    _lib.check(ctx.lib.pyas_moments_combine_segments(ctx.handle, in_ptr, index_ptr, seg_ptr, int(n_seg), out_ptr,
+                                                     stream), "pyas_moments_combine_segments")
+
+
+def moments_combine_grid(ctx: Context, in_ptr, grid: _lib.Grid, out_ptr, stream) -> None:
+    _lib.check(ctx.lib.pyas_moments_combine_grid(ctx.handle, in_ptr, ctypes.byref(grid), out_ptr, stream),
+               "pyas_moments_combine_grid")
 
 
 _FORMAT = {"sum": _lib.FORMAT_SUM, "min": _lib.FORMAT_MIN, "max": _lib.FORMAT_MAX,
