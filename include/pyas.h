@@ -554,6 +554,42 @@ int pyas_moments_combine_segments(pyas_ctx *ctx, const pyas_moments *in, const i
 int pyas_moments_combine_grid(pyas_ctx *ctx, const pyas_moments *in, const pyas_grid *grid,
                               pyas_moments *out, void *stream);
 
+/* ---- weighted sums (Active.mean / Active.sum with weights=) -----------------
+ * Partial record of a weighted mean over a set of elements (32 bytes):
+ * count unmasked elements; sw = sum w; swx = sum w x  (f64).  The all-zero
+ * record is neutral and records merge by plain f64 addition of each field, in
+ * the fixed order of the moments records (lanes pairwise at distance 1, 2,
+ * 4..., waves in wave order, tiles in tile order, chunks in the order of the
+ * combines), so results are bit-identical from run to run.
+ * The weight of an element is the product of one factor per chunk dim,
+ *   w = ((1 * f_0) * f_1) * ... * f_{ndim-1},   f_d = pool[origin[c][d] + i_d],
+ * multiplied in ascending dim order (the leading 1 is exact), where i_d is the
+ * element's index inside chunk c along dim d: slices, strides and index lists
+ * look up the same way.  A dim without weights points at a run of 1.0.  Every
+ * factor of a chunk must be readable: pool[origin[c][d] .. + chunk_shape[d]).
+ * x converts to f64 as astype(float64) does; a lane adds w to sw and
+ * fma(w, x, swx) to swx.  Masked elements are excluded by select, never
+ * multiplied by 0; an unmasked NaN gives a NaN swx. */
+typedef struct { int64_t count; double sw; double swx; uint64_t reserved; } pyas_wsum;
+
+typedef struct {
+    const double *pool;      /* device: the per-dim factor vectors, concatenated */
+    const int32_t *origin;   /* device [n_chunks * PYAS_MAX_DIMS]: index in pool of the factor
+                                of chunk c's local index 0 along dim d */
+} pyas_weights;
+
+/* pyas_moments_axes for weighted sums: same outputs, out_offsets and errors;
+ * PYAS_EINVAL when weights or one of its pointers is NULL. */
+int pyas_wsum_axes(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask,
+                   const pyas_weights *weights, uint32_t axes_mask, const int64_t *out_offsets,
+                   pyas_wsum *out, void *stream);
+/* pyas_combine_segments / pyas_combine_grid for weighted-sum records (same orders). */
+int pyas_wsum_combine_segments(pyas_ctx *ctx, const pyas_wsum *in, const int64_t *index,
+                               const int64_t *seg_offsets, int64_t n_segments, pyas_wsum *out,
+                               void *stream);
+int pyas_wsum_combine_grid(pyas_ctx *ctx, const pyas_wsum *in, const pyas_grid *grid,
+                           pyas_wsum *out, void *stream);
+
 /* Result formatting on the device: the last step of Active._from_storage
  * (active.py:591-630) applied to n combined partials (device), so that only
  * the result's values and mask cross PCIe (9-16 bytes per output instead of

@@ -43,6 +43,17 @@ class Moments(ctypes.Structure):
                 ("reserved", ctypes.c_uint64)]
 
 
+class Wsum(ctypes.Structure):
+    """pyas_wsum: count, sum w and sum w x of a set of elements."""
+    _fields_ = [("count", ctypes.c_int64), ("sw", ctypes.c_double), ("swx", ctypes.c_double),
+                ("reserved", ctypes.c_uint64)]
+
+
+class Weights(ctypes.Structure):
+    """pyas_weights: the per-dim factor vectors and each chunk's origin in them (device pointers)."""
+    _fields_ = [("pool", ctypes.c_void_p), ("origin", ctypes.c_void_p)]
+
+
 class Mask(ctypes.Structure):
     _fields_ = [
         ("flags", ctypes.c_uint32),
@@ -151,6 +162,8 @@ PARTIAL_NBYTES = ctypes.sizeof(Partial)
 assert PARTIAL_NBYTES == 32
 MOMENTS_NBYTES = ctypes.sizeof(Moments)
 assert MOMENTS_NBYTES == 32
+WSUM_NBYTES = ctypes.sizeof(Wsum)
+assert WSUM_NBYTES == 32
 
 _vp = ctypes.c_void_p
 _i32 = ctypes.c_int32
@@ -207,6 +220,10 @@ SIGNATURES = {
     "pyas_moments_axes": [_vp, ctypes.POINTER(Batch), ctypes.POINTER(Mask), _u32, _vp, _vp, _vp],
     "pyas_moments_combine_segments": [_vp, _vp, _vp, _vp, _i64, _vp, _vp],
     "pyas_moments_combine_grid": [_vp, _vp, ctypes.POINTER(Grid), _vp, _vp],
+    "pyas_wsum_axes": [_vp, ctypes.POINTER(Batch), ctypes.POINTER(Mask), ctypes.POINTER(Weights), _u32, _vp, _vp,
+                       _vp],
+    "pyas_wsum_combine_segments": [_vp, _vp, _vp, _vp, _i64, _vp, _vp],
+    "pyas_wsum_combine_grid": [_vp, _vp, ctypes.POINTER(Grid), _vp, _vp],
     "pyas_format_partials": [_vp, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _vp],
     "pyas_unshuffle": [_vp, _vp, _vp, _i64, _i32, _vp],
     "pyas_unshuffle_chunks": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp],

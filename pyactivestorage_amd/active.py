@@ -27,7 +27,10 @@ the reference), or a :class:`~pyactivestorage_amd.variable.ChunkedVariable`.
 
 Beyond the reference: ``.var(axis, ddof)`` / ``.std(axis, ddof)``, one pass of
 count / mean / m2 records (``pyas_moments_axes``) merged with Chan's formula
-in the order the sums are combined in (``_reduce_moments``).
+in the order the sums are combined in (``_reduce_moments``); and
+``.mean(axis, weights={dim: vector})`` / ``.sum(axis, weights=...)``, count /
+sum w / sum w x records (``pyas_wsum_axes``) merged by addition
+(``_reduce_weighted``).
 """
 from __future__ import annotations
 
@@ -39,7 +42,7 @@ import warnings
 
 import numpy as np
 
-from . import _lib, engine, moments, selection, zerosign
+from . import _lib, engine, moments, selection, weighted, zerosign
 from .batch import ReductionPlan, _all_full
 from .device import DeviceBuffer, get_context
 from .dtypes import native, sum_dtype
@@ -52,6 +55,7 @@ from .variable import ChunkedVariable, decode_filters, get_missing_attributes
 
 _ALIGN = 256
 _MOMENTS_SEG = 64   # records a thread folds per level of a full var / std reduction
+_WSUM_SEG = 64      # the same for a full weighted mean / sum reduction
 _RESIDENT_LOCK = threading.Lock()
 _RESIDENT_CV = threading.Condition(_RESIDENT_LOCK)   # slot state changes
 _EMPTY, _LOADING, _LOADED = 0, 1, 2
@@ -319,6 +323,7 @@ class Active:
         self._components = False
         self._method = None
         self._ddof = 0                  # var / std: the divisor is count - ddof
+        self._weights = None            # mean / sum: {dim: float64 vector} of the next query
         self._max_threads = int(max_threads)
         self.device = device
         # f3: zlib chunks inflate on the GPU (True), on the host reader threads
@@ -358,8 +363,55 @@ class Active:
             raise ValueError(f"Bad 'method': {value}. Choose from min/max/mean/sum.")
         self._method = value
         self._ddof = 0
+        self._weights = None
 
-    def mean(self, axis=None):
+    @property
+    def weights(self):
+        """The weights of the next query (``{dim: float64 vector}``) or None."""
+        return self._weights
+
+    @weights.setter
+    def weights(self, value):
+        self._weights = self._check_weights(value)
+
+    def _check_weights(self, weights):
+        """``{dim: 1-D array-like}`` as ``{dim >= 0: float64 vector}``: each
+        vector has ``shape[dim]`` entries (it is indexed by the global index
+        along ``dim``), all finite and >= 0.  ValueError otherwise."""
+        if weights is None:
+            return None
+        if not hasattr(weights, "items"):
+            raise ValueError("weights must be a mapping {dim: 1-D array-like}")
+        ndim, shape = self.ds.ndim, self.ds.shape
+        out = {}
+        for dim, w in weights.items():
+            if isinstance(dim, (bool, np.bool_)) or not isinstance(dim, (int, np.integer)) or not -ndim <= dim < ndim:
+                raise ValueError(f"weights: dimension {dim!r} is out of range for {ndim} dimensions")
+            d = int(dim) % ndim
+            if d in out:
+                raise ValueError(f"weights: dimension {d} is given twice")
+            try:
+                w = np.asarray(w, dtype=np.float64)
+            except (TypeError, ValueError) as exc:
+                raise ValueError(f"weights[{dim!r}] is not numeric: {exc}") from None
+            if w.ndim != 1 or w.size != shape[d]:
+                raise ValueError(f"weights[{dim!r}] must be 1-D with {shape[d]} entries. Got shape {w.shape}")
+            if not np.all(np.isfinite(w)) or np.any(w < 0):
+                raise ValueError(f"weights[{dim!r}] has a negative, NaN or infinite entry")
+            out[d] = w
+        return out
+
+    def mean(self, axis=None, weights=None):
+        """Mean of the unmasked elements.  With ``weights = {dim: vector}`` the
+        weighted mean ``sum(w x) / sum(w)`` in float64, where an element's
+        weight is the product of its dims' entries (dims not named: 1),
+        multiplied in ascending dim order.  The result is masked where
+        ``sum(w) == 0``: no unmasked element, or every unmasked element has
+        weight exactly 0 (``np.ma.average`` gives NaN for such a full
+        reduction; here it is masked).  With ``components`` the result is
+        ``{"sum": sum(w x), "sum_of_weights": sum(w), "n": count}``."""
+        if weights is not None:
+            self._weights = self._check_weights(weights)
         self._method = "mean"
         if axis is not None:
             self._axis = axis
@@ -377,7 +429,12 @@ class Active:
             self._axis = axis
         return self
 
-    def sum(self, axis=None):
+    def sum(self, axis=None, weights=None):
+        """Sum of the unmasked elements; with ``weights`` (see :meth:`mean`)
+        the weighted sum ``sum(w x)`` in float64, masked where no element is
+        unmasked.  With ``components``: ``{"sum": sum(w x), "n": count}``."""
+        if weights is not None:
+            self._weights = self._check_weights(weights)
         self._method = "sum"
         if axis is not None:
             self._axis = axis
@@ -411,6 +468,7 @@ class Active:
             return self._get_selection(index)
         finally:
             self._method = None          # active.py:633
+            self._weights = None         # weights are per query
             for store in held:
                 _unhold(store)
             self._held.stores = []
@@ -420,13 +478,18 @@ class Active:
         second = self._method in ("var", "std")
         if second and self.group is not None:
             raise NotImplementedError("var/std with group=…: second moments are reduced on one GPU only")
+        has_w = self._weights is not None
+        if has_w and self._method not in ("mean", "sum"):
+            raise ValueError(f"weights apply to mean and sum only, not to method {self._method!r}")
+        if has_w and self.group is not None:
+            raise NotImplementedError("weights with group=…: weighted sums are reduced on one GPU only")
         if self._axis is None:
             self._axis = tuple(range(ds.ndim))
         elif isinstance(self._axis, int):
             self._axis = (self._axis,)
         cache_key = None
-        # (var / std bypass the plan cache: its plans replay pyas_partial launches)
-        if self.resident and self.group is None and self._method is not None and not second:
+        # (var / std and weighted queries bypass the plan cache: its plans replay pyas_partial launches)
+        if self.resident and self.group is None and self._method is not None and not second and not has_w:
             ikey = _index_key(index)
             if ikey is not None:
                 cache_key = (ikey, self._norm_axes(), _missing_key(self.missing))
@@ -446,6 +509,8 @@ class Active:
                                  f"axis {i!r} drops the axis.")
         if second:
             return self._reduce_moments(indexer, compressor, filters, self._norm_axes())
+        if has_w:
+            return self._reduce_weighted(indexer, compressor, filters, self._norm_axes())
         return self._reduce(indexer, compressor, filters, self._norm_axes(), cache_key)
 
     def _norm_axes(self):
@@ -922,6 +987,141 @@ class Active:
         del keep
         return self._format_moments(final.reshape(final_shape))
 
+    # -- weighted mean / sum ------------------------------------------------------
+    def _weight_tables(self, coords):
+        """pyas_weights of this query for the chunks at ``coords``: the pool (a
+        run of 1.0 for the dims without weights, then each weighted dim's
+        vector, zero-padded to whole chunks so that every factor of an edge
+        chunk is readable) and each chunk's origin in it."""
+        ds = self.ds
+        coords = np.asarray(coords, dtype=np.int64).reshape(-1, ds.ndim)
+        parts, pos = [np.ones(max(ds.chunks), dtype=np.float64)], max(ds.chunks)
+        origin = np.zeros((len(coords), _lib.MAX_DIMS), dtype=np.int64)
+        for d in sorted(self._weights):
+            padded = np.zeros(-(-ds.shape[d] // ds.chunks[d]) * ds.chunks[d], dtype=np.float64)
+            padded[:ds.shape[d]] = self._weights[d]
+            origin[:, d] = pos + coords[:, d] * ds.chunks[d]
+            parts.append(padded)
+            pos += padded.size
+        if pos >= 2 ** 31:
+            raise NotImplementedError("weight vectors of 2^31 entries or more")
+        return np.concatenate(parts), origin.astype(np.int32)
+
+    def _reduce_weighted(self, indexer, compressor, filters, axes):
+        """mean / sum with weights: per-chunk count / sum w / sum w x records
+        (pyas_wsum_axes) added up in the order :meth:`_reduce_moments` merges
+        its records in: a full reduction in chunk order, a box query over the
+        chunk layers of each output (pyas_wsum_combine_grid), anything else
+        over host-built segments (pyas_wsum_combine_segments)."""
+        ds = self.ds
+        final_shape = tuple(1 if i in axes else n for i, n in enumerate(indexer.shape))
+        n_final = int(np.prod(final_shape))
+        final = np.zeros(n_final, dtype=engine.wsum_dtype)
+        fmt = self._format_weighted
+        box = self._box_plan(indexer)
+        dims = None
+        if box is not None:
+            dims, coords, table, pool = box
+            n = len(coords)
+        else:
+            chunk_list = list(indexer)
+            n = len(chunk_list)
+        if n == 0 or n_final == 0:
+            return fmt(final.reshape(final_shape))
+        if box is not None:
+            ctx, st, buf, offsets, fused = self._ingest(coords, compressor, filters)
+            full = _all_full(table, ds.chunks)
+            plan = ReductionPlan(ctx, ds.dtype, ds.chunks, buf.ptr, offsets, shuffle=fused,
+                                 sel_table=None if full else table, index_pool=None if full else pool,
+                                 missing=self.missing, stream=st)
+        else:
+            ctx, st, buf, offsets, fused = self._ingest([c for c, _ in chunk_list], compressor, filters)
+            sels = [self._chunk_sel(projs) for _, projs in chunk_list]
+            plan = ReductionPlan(ctx, ds.dtype, ds.chunks, buf.ptr, offsets, shuffle=fused, selections=sels,
+                                 missing=self.missing, stream=st)
+        axes_mask = 0
+        for a in axes:
+            axes_mask |= 1 << a
+        nb = _lib.WSUM_NBYTES
+        fin = DeviceBuffer(ctx, n_final * nb)
+        wpool, worigin = self._weight_tables(coords if box is not None else [c for c, _ in chunk_list])
+        wbuf = DeviceBuffer(ctx, wpool.nbytes + worigin.nbytes)
+        ctx.h2d(wbuf.ptr, wpool, st)
+        ctx.h2d(wbuf.ptr + wpool.nbytes, worigin, st)
+        keep = [buf, wbuf]
+
+        def reduce_axes(off_ptr, out_ptr, st):
+            engine.wsum_axes(ctx, plan.batch, plan.mask_up.struct, wbuf.ptr, wbuf.ptr + wpool.nbytes, axes_mask,
+                             off_ptr, out_ptr, st)
+        if len(axes) == ds.ndim:
+            # one record per chunk, folded in chunk order: groups of _WSUM_SEG
+            # consecutive records per thread, level after level (a fixed
+            # function of the chunk count alone)
+            # (one allocation: every level's records, then every level's segment bounds)
+            levels, m = [], n
+            while True:
+                n_seg = -(-m // _WSUM_SEG)
+                levels.append((n_seg, np.minimum(np.arange(n_seg + 1, dtype=np.int64) * _WSUM_SEG, m)))
+                if n_seg == 1:
+                    break
+                m = n_seg
+            segs = np.concatenate([seg for _, seg in levels])
+            n_rec = n + sum(n_seg for n_seg, _ in levels[:-1])
+            work = DeviceBuffer(ctx, n_rec * nb + segs.nbytes)
+            keep.append(work)
+            cur, sptr = work.ptr, work.ptr + n_rec * nb
+            ctx.h2d(sptr, segs, st)
+            reduce_axes(None, cur, st)
+            nxt = cur + n * nb
+            for n_seg, seg in levels:
+                dst = fin.ptr if n_seg == 1 else nxt
+                engine.wsum_combine_segments(ctx, cur, None, sptr, n_seg, dst, st)
+                cur, nxt, sptr = dst, dst + n_seg * nb, sptr + seg.nbytes
+        elif dims is not None:
+            out_off, tables = self._grid_from_dims(dims, axes, final_shape)
+            obuf = DeviceBuffer(ctx, out_off.nbytes)
+            ctx.h2d(obuf.ptr, out_off, st)
+            tbuf = DeviceBuffer(ctx, max(tables["blob"].nbytes, 16))
+            ctx.h2d(tbuf.ptr, tables["blob"], st)
+            g = _lib.Grid()
+            g.ndim = ds.ndim
+            g.axes_mask = axes_mask
+            for d in range(ds.ndim):
+                g.n_coords[d] = tables["n_coords"][d]
+                g.out_extent[d] = final_shape[d] if d not in axes else 1
+                if d not in axes:
+                    g.pos_coord[d] = tbuf.ptr + 4 * tables["pos_coord"][d]
+                    g.pos_local[d] = tbuf.ptr + 4 * tables["pos_local"][d]
+                    g.coord_count[d] = tbuf.ptr + 4 * tables["coord_count"][d]
+            g.chunk_out_offsets = obuf.ptr
+            parts = DeviceBuffer(ctx, max(int(tables["n_parts"]), 1) * nb)
+            reduce_axes(obuf.ptr, parts.ptr, st)
+            engine.wsum_combine_grid(ctx, parts.ptr, g, fin.ptr, st)
+            keep += [obuf, tbuf, parts]
+        else:
+            sizes, fidx = [], []
+            for _, projs in chunk_list:
+                pos = [p.out_pos if i not in axes else np.zeros(1, dtype=np.int64) for i, p in enumerate(projs)]
+                grids = np.meshgrid(*pos, indexing="ij")
+                fidx.append(np.ravel_multi_index([x.reshape(-1) for x in grids], final_shape))
+                sizes.append(grids[0].size)
+            out_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+            f_all = np.concatenate(fidx)
+            order = np.argsort(f_all, kind="stable").astype(np.int64)
+            seg = np.searchsorted(f_all[order], np.arange(n_final + 1)).astype(np.int64)
+            meta = np.concatenate([out_off[:-1], order, seg])
+            mbuf = DeviceBuffer(ctx, meta.nbytes)
+            ctx.h2d(mbuf.ptr, meta, st)
+            parts = DeviceBuffer(ctx, max(int(out_off[-1]), 1) * nb)
+            reduce_axes(mbuf.ptr, parts.ptr, st)
+            engine.wsum_combine_segments(ctx, parts.ptr, mbuf.ptr + 8 * n, mbuf.ptr + 8 * (n + order.size),
+                                            n_final, fin.ptr, st)
+            keep += [mbuf, parts]
+        ctx.d2h(final, fin.ptr, st)
+        ctx.synchronize(st)
+        del keep
+        return fmt(final.reshape(final_shape))
+
     def _format_moments(self, parts):
         """The float64 result of a var / std query from its combined records
         (moments.finalize), or its components."""
@@ -932,6 +1132,19 @@ class Active:
                     "n": np.ma.MaskedArray(np.ascontiguousarray(parts["count"]),
                                            mask=np.zeros(parts.shape, dtype=bool))}
         return moments.finalize(parts, self._ddof, std=self._method == "std")
+
+    def _format_weighted(self, parts):
+        """The float64 result of a weighted mean / sum query from its combined
+        records (weighted.finalize), or its components."""
+        if self._components:
+            empty = parts["count"] == 0
+            out = {"sum": np.ma.MaskedArray(np.ascontiguousarray(parts["swx"]), mask=empty),
+                   "n": np.ma.MaskedArray(np.ascontiguousarray(parts["count"]),
+                                          mask=np.zeros(parts.shape, dtype=bool))}
+            if self._method == "mean":
+                out["sum_of_weights"] = np.ma.MaskedArray(np.ascontiguousarray(parts["sw"]), mask=empty)
+            return out
+        return weighted.finalize(parts, mean=self._method == "mean")
 
     def _tie_which(self) -> int:
         """1 / 2 when the query's min / max of a float variable must give

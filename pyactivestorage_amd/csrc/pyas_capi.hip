@@ -1573,6 +1573,101 @@ int pyas_moments_combine_grid(pyas_ctx *ctx, const pyas_moments *in, const pyas_
     return PYAS_OK;
 }
 
+int pyas_wsum_axes(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask, const pyas_weights *weights,
+                   uint32_t axes_mask, const int64_t *out_offsets, pyas_wsum *out, void *stream) {
+    if (!ctx) return fail(PYAS_EINVAL, "ctx is NULL");
+    if (batch && (batch->ndim < 1 || batch->ndim > PYAS_MAX_DIMS))
+        return fail(PYAS_ENOTSUP, "chunk rank %d outside 1..%d", batch->ndim, PYAS_MAX_DIMS);
+    pyas::WsumArgs x;
+    std::memset(&x, 0, sizeof(x));
+    int es;
+    bool shuf, bsw, masked;
+    int rc = prepare(ctx, batch, mask, x.r, es, shuf, bsw, masked);
+    if (rc) return rc;
+    if (axes_mask >> batch->ndim) return fail(PYAS_EINVAL, "axes mask 0x%x beyond rank %d", axes_mask, batch->ndim);
+    const int64_t n = batch->n_chunks;
+    if (n == 0) return PYAS_OK;
+    if (!weights || !weights->pool || !weights->origin) return fail(PYAS_EINVAL, "weights is NULL or has a NULL table");
+    if (!out) return fail(PYAS_EINVAL, "out is NULL");
+    PYAS_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    x.axes = axes_mask;
+    x.out_offsets = out_offsets;
+    x.out = out;
+    x.wpool = weights->pool;
+    x.worigin = weights->origin;
+    x.bswap = bsw;
+    x.masked = masked;
+    if (axes_mask == (1u << batch->ndim) - 1u) {
+        // every dim reduced: a workgroup per (chunk, tile); tiles merge in tile order
+        const int64_t tpc = tiles_per_chunk(ctx, x.r.chunk_elems * es);
+        const int64_t grid = n * tpc;
+        if (grid >= (int64_t(1) << 31)) return fail(PYAS_ENOTSUP, "grid of %lld workgroups", (long long)grid);
+        x.bpc = tpc;
+        if (tpc > 1) {
+            void *scr = nullptr;
+            rc = ensure_scratch(ctx, stream, (size_t)grid * sizeof(pyas_wsum), &scr);
+            if (rc) return rc;
+            x.tiles = (pyas_wsum *)scr;
+        }
+        PYAS_HIP(pyas::launch_wsum_full(batch->dtype, x, shuf, grid, st));
+        if (tpc > 1) PYAS_HIP(pyas::launch_wsum_tiles(x.tiles, tpc, n, out_offsets, out, st));
+        return PYAS_OK;
+    }
+    if (!out_offsets) return fail(PYAS_EINVAL, "out_offsets is NULL");
+    int64_t keep_elems = 1;
+    for (int d = 0; d < batch->ndim; ++d)
+        if (!((axes_mask >> d) & 1u)) keep_elems *= batch->chunk_shape[d];
+    x.row = ((axes_mask >> (batch->ndim - 1)) & 1u) != 0;
+    // outputs per workgroup pass, as in pyas_moments_axes
+    const int64_t per_block = x.row ? (pyas::kBlock / pyas::kWave) * 16 : pyas::kBlock;
+    int64_t bpc = (keep_elems + per_block - 1) / per_block;
+    if (bpc > 64) bpc = 64;
+    if (bpc < 1) bpc = 1;
+    x.bpc = bpc;
+    const int64_t grid = n * bpc;
+    if (grid >= (int64_t(1) << 31)) return fail(PYAS_ENOTSUP, "grid too large");
+    PYAS_HIP(pyas::launch_wsum_axes(batch->dtype, x, shuf, grid, st));
+    return PYAS_OK;
+}
+
+int pyas_wsum_combine_segments(pyas_ctx *ctx, const pyas_wsum *in, const int64_t *index,
+                               const int64_t *seg_offsets, int64_t n_segments, pyas_wsum *out, void *stream) {
+    if (!ctx) return fail(PYAS_EINVAL, "ctx is NULL");
+    if (n_segments < 0) return fail(PYAS_EINVAL, "negative segment count");
+    if (n_segments == 0) return PYAS_OK;
+    if (!in || !seg_offsets || !out) return fail(PYAS_EINVAL, "NULL argument");
+    PYAS_HIP(hipSetDevice(ctx->device));
+    PYAS_HIP(pyas::launch_wsum_segments(in, index, seg_offsets, n_segments, out, (hipStream_t)stream));
+    return PYAS_OK;
+}
+
+int pyas_wsum_combine_grid(pyas_ctx *ctx, const pyas_wsum *in, const pyas_grid *g, pyas_wsum *out,
+                           void *stream) {
+    // (the checks of pyas_moments_combine_grid)
+    if (!ctx) return fail(PYAS_EINVAL, "ctx is NULL");
+    if (!g) return fail(PYAS_EINVAL, "grid is NULL");
+    if (g->ndim < 1 || g->ndim > PYAS_MAX_DIMS)
+        return fail(PYAS_ENOTSUP, "grid rank %d outside 1..%d", g->ndim, PYAS_MAX_DIMS);
+    if (g->axes_mask >> g->ndim) return fail(PYAS_EINVAL, "axes mask 0x%x beyond rank %d", g->axes_mask, g->ndim);
+    int64_t n_out = 1, n_layers = 1;
+    for (int d = 0; d < g->ndim; ++d) {
+        if (g->n_coords[d] < 1) return fail(PYAS_EINVAL, "n_coords[%d] = %lld", d, (long long)g->n_coords[d]);
+        if ((g->axes_mask >> d) & 1u) {
+            n_layers *= g->n_coords[d];
+        } else {
+            if (g->out_extent[d] < 1) return fail(PYAS_EINVAL, "out_extent[%d] = %lld", d, (long long)g->out_extent[d]);
+            if (!g->pos_coord[d] || !g->pos_local[d] || !g->coord_count[d])
+                return fail(PYAS_EINVAL, "kept dim %d has a NULL table", d);
+            n_out *= g->out_extent[d];
+        }
+    }
+    if (!in || !out || !g->chunk_out_offsets) return fail(PYAS_EINVAL, "NULL argument");
+    PYAS_HIP(hipSetDevice(ctx->device));
+    PYAS_HIP(pyas::launch_wsum_grid(in, *g, n_out, n_layers, out, (hipStream_t)stream));
+    return PYAS_OK;
+}
+
 int pyas_format_partials(pyas_ctx *ctx, int32_t dtype, const pyas_partial *in, int64_t n,
                          int32_t method, void *values, uint8_t *mask, int64_t *counts,
                          void *stream) {

@@ -274,6 +274,27 @@ hipError_t launch_moments_segments(const pyas_moments *in, const int64_t *index,
                                    int64_t n_seg, pyas_moments *out, hipStream_t st);
 hipError_t launch_moments_grid(const pyas_moments *in, const pyas_grid &g, int64_t n_out, int64_t n_layers,
                                pyas_moments *out, hipStream_t st);
+// weighted sums (pyas_weighted.hip): count / sum w / sum w x records
+struct WsumArgs {
+    ReduceArgs r;                     // r.out unused
+    uint32_t axes;                    // reduced dims
+    int64_t bpc;                      // workgroups per chunk (full: tiles per chunk)
+    const int64_t *out_offsets;       // NULL (full only): chunk c's record at out[c]
+    pyas_wsum *out;
+    pyas_wsum *tiles;                 // full with bpc > 1: one record per workgroup
+    const double *wpool;              // pyas_weights
+    const int32_t *worigin;
+    bool bswap, masked;
+    bool row;                         // innermost dim reduced: a wave per output
+};
+hipError_t launch_wsum_full(int dtype, const WsumArgs &a, bool shuf, int64_t grid, hipStream_t st);
+hipError_t launch_wsum_axes(int dtype, const WsumArgs &a, bool shuf, int64_t grid, hipStream_t st);
+hipError_t launch_wsum_tiles(const pyas_wsum *tiles, int64_t tpc, int64_t n_chunks, const int64_t *out_offsets,
+                             pyas_wsum *out, hipStream_t st);
+hipError_t launch_wsum_segments(const pyas_wsum *in, const int64_t *index, const int64_t *seg, int64_t n_seg,
+                                pyas_wsum *out, hipStream_t st);
+hipError_t launch_wsum_grid(const pyas_wsum *in, const pyas_grid &g, int64_t n_out, int64_t n_layers,
+                            pyas_wsum *out, hipStream_t st);
 // host ingest (pyas_ingest.hip): pread ring -> pinned slots -> H2D
 struct Ingest;
 Ingest *ingest_create(int device);

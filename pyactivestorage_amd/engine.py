@@ -28,6 +28,9 @@ def partial_dtype(dt) -> np.dtype:
 # Host view of ``pyas_moments`` (every storage dtype: the record is f64)
 moments_dtype = np.dtype([("count", "<i8"), ("mean", "<f8"), ("m2", "<f8"), ("reserved", "<u8")])
 
+# Host view of ``pyas_wsum``
+wsum_dtype = np.dtype([("count", "<i8"), ("sw", "<f8"), ("swx", "<f8"), ("reserved", "<u8")])
+
 
 @dataclass
 class Layout:
@@ -233,6 +236,26 @@ def moments_combine_segments(ctx: Context, in_ptr, index_ptr, seg_ptr, n_seg, ou
 def moments_combine_grid(ctx: Context, in_ptr, grid: _lib.Grid, out_ptr, stream) -> None:
     _lib.check(ctx.lib.pyas_moments_combine_grid(ctx.handle, in_ptr, ctypes.byref(grid), out_ptr, stream),
                "pyas_moments_combine_grid")
+
+
+def wsum_axes(ctx: Context, batch: _lib.Batch, mask: _lib.Mask, pool_ptr, origin_ptr, axes_mask: int,
+              out_offsets_ptr, out_ptr, stream) -> None:
+    """pyas_wsum_axes: count / sum w / sum w x records per chunk output, laid
+    out like :func:`moments_axes`'; ``pool_ptr`` / ``origin_ptr``: pyas_weights."""
+    w = _lib.Weights(pool_ptr, origin_ptr)
+    _lib.check(ctx.lib.pyas_wsum_axes(ctx.handle, ctypes.byref(batch), ctypes.byref(mask), ctypes.byref(w),
+                                      int(axes_mask), out_offsets_ptr, out_ptr, stream), "pyas_wsum_axes")
+
+
+def wsum_combine_segments(ctx: Context, in_ptr, index_ptr, seg_ptr, n_seg, out_ptr, stream) -> None:
+    """pyas_wsum_combine_segments (``index_ptr`` None: the identity)."""
+    _lib.check(ctx.lib.pyas_wsum_combine_segments(ctx.handle, in_ptr, index_ptr, seg_ptr, int(n_seg), out_ptr,
+                                                  stream), "pyas_wsum_combine_segments")
+
+
+def wsum_combine_grid(ctx: Context, in_ptr, grid: _lib.Grid, out_ptr, stream) -> None:
+    _lib.check(ctx.lib.pyas_wsum_combine_grid(ctx.handle, in_ptr, ctypes.byref(grid), out_ptr, stream),
+               "pyas_wsum_combine_grid")
 
 
 _FORMAT = {"sum": _lib.FORMAT_SUM, "min": _lib.FORMAT_MIN, "max": _lib.FORMAT_MAX,
