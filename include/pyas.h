@@ -590,6 +590,42 @@ int pyas_wsum_combine_segments(pyas_ctx *ctx, const pyas_wsum *in, const int64_t
 int pyas_wsum_combine_grid(pyas_ctx *ctx, const pyas_wsum *in, const pyas_grid *grid,
                            pyas_wsum *out, void *stream);
 
+/* ---- binned counts (Active.histogram) -----------------------------------------
+ * Bin rule, over n_bins + 1 strictly increasing finite f64 edges e: an
+ * unmasked selected element x (converted to f64 as astype(float64) does)
+ * counts in bin i when e[i] <= x < e[i+1]; the last bin also holds
+ * x == e[n_bins]; x < e[0] and -inf count as `below`, x > e[n_bins] and +inf
+ * as `above`, NaN as `nan`.  Masked elements count nowhere.
+ * Table row of one output: n_bins counts, then below, above, nan: n_bins + 3
+ * int64.  Counts are added to the table, which the caller zeroes
+ * (pyas_hist_reset); integer adds commute, so results are exact and
+ * bit-identical from run to run.
+ * For uniform edges (PYAS_HIST_UNIFORM) the kernels guess the bin as
+ * (x - lo) * scale, lo = e[0], scale = n_bins / (e[n_bins] - e[0]); the guess is
+ * only a starting point, the edge table decides. */
+#define PYAS_HIST_UNIFORM 1u
+#define PYAS_HIST_MAX_BINS (1 << 20)
+typedef struct {
+    const double *edges;     /* device: n_bins + 1 edges */
+    int32_t n_bins;
+    uint32_t flags;          /* PYAS_HIST_* */
+    double lo;               /* PYAS_HIST_UNIFORM: e[0] */
+    double scale;            /* PYAS_HIST_UNIFORM: n_bins / (e[n_bins] - e[0]) */
+} pyas_hist;
+
+/* pyas_moments_axes for binned counts (same argument checks and errors):
+ * output o (C order over the kept selected dims) of chunk c adds into table
+ * row out_index[out_offsets[c] + o], or row out_offsets[c] + o when out_index
+ * is NULL (both device).  With every dim in axes_mask a chunk has one output
+ * and out_offsets may be NULL: every chunk adds into row 0; up to 2,048 bins
+ * count in LDS and each workgroup adds its table once.  PYAS_EINVAL when hist,
+ * its edges or table is NULL, n_bins < 1 or n_bins > PYAS_HIST_MAX_BINS. */
+int pyas_hist_axes(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask,
+                   const pyas_hist *hist, uint32_t axes_mask, const int64_t *out_offsets,
+                   const int64_t *out_index, int64_t *table, void *stream);
+/* Zero n_rows table rows of n_bins + 3 int64 on the stream. */
+int pyas_hist_reset(pyas_ctx *ctx, int64_t *table, int64_t n_rows, int32_t n_bins, void *stream);
+
 /* Result formatting on the device: the last step of Active._from_storage
  * (active.py:591-630) applied to n combined partials (device), so that only
  * the result's values and mask cross PCIe (9-16 bytes per output instead of

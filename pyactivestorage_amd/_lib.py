@@ -54,6 +54,16 @@ class Weights(ctypes.Structure):
     _fields_ = [("pool", ctypes.c_void_p), ("origin", ctypes.c_void_p)]
 
 
+class Hist(ctypes.Structure):
+    """pyas_hist: device edges (n_bins + 1), PYAS_HIST_* flags and the uniform guess (lo, scale)."""
+    _fields_ = [("edges", ctypes.c_void_p), ("n_bins", ctypes.c_int32), ("flags", ctypes.c_uint32),
+                ("lo", ctypes.c_double), ("scale", ctypes.c_double)]
+
+
+HIST_UNIFORM = 1
+HIST_MAX_BINS = 1 << 20
+
+
 class Mask(ctypes.Structure):
     _fields_ = [
         ("flags", ctypes.c_uint32),
@@ -224,6 +234,9 @@ SIGNATURES = {
                        _vp],
     "pyas_wsum_combine_segments": [_vp, _vp, _vp, _vp, _i64, _vp, _vp],
     "pyas_wsum_combine_grid": [_vp, _vp, ctypes.POINTER(Grid), _vp, _vp],
+    "pyas_hist_axes": [_vp, ctypes.POINTER(Batch), ctypes.POINTER(Mask), ctypes.POINTER(Hist), _u32, _vp, _vp, _vp,
+                       _vp],
+    "pyas_hist_reset": [_vp, _vp, _i64, _i32, _vp],
     "pyas_format_partials": [_vp, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _vp],
     "pyas_unshuffle": [_vp, _vp, _vp, _i64, _i32, _vp],
     "pyas_unshuffle_chunks": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp],

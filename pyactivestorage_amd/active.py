@@ -27,10 +27,12 @@ the reference), or a :class:`~pyactivestorage_amd.variable.ChunkedVariable`.
 
 Beyond the reference: ``.var(axis, ddof)`` / ``.std(axis, ddof)``, one pass of
 count / mean / m2 records (``pyas_moments_axes``) merged with Chan's formula
-in the order the sums are combined in (``_reduce_moments``); and
+in the order the sums are combined in (``_reduce_moments``);
 ``.mean(axis, weights={dim: vector})`` / ``.sum(axis, weights=...)``, count /
 sum w / sum w x records (``pyas_wsum_axes``) merged by addition
-(``_reduce_weighted``).
+(``_reduce_weighted``); and ``.histogram(bins, range, axis)``, int64 counts
+added by every chunk straight into the result table (``pyas_hist_axes``,
+``_reduce_hist``).
 """
 from __future__ import annotations
 
@@ -42,7 +44,7 @@ import warnings
 
 import numpy as np
 
-from . import _lib, engine, moments, selection, weighted, zerosign
+from . import _lib, engine, histogram, moments, selection, weighted, zerosign
 from .batch import ReductionPlan, _all_full
 from .device import DeviceBuffer, get_context
 from .dtypes import native, sum_dtype
@@ -324,6 +326,7 @@ class Active:
         self._method = None
         self._ddof = 0                  # var / std: the divisor is count - ddof
         self._weights = None            # mean / sum: {dim: float64 vector} of the next query
+        self._hist = None               # histogram: the bins of the next query (_check_hist)
         self._max_threads = int(max_threads)
         self.device = device
         # f3: zlib chunks inflate on the GPU (True), on the host reader threads
@@ -364,6 +367,7 @@ class Active:
         self._method = value
         self._ddof = 0
         self._weights = None
+        self._hist = None
 
     @property
     def weights(self):
@@ -450,6 +454,38 @@ class Active:
         """Standard deviation: the square root of :meth:`var`."""
         return self._set_moments("std", axis, ddof)
 
+    def histogram(self, bins=10, range=None, axis=None):   # noqa: A002 - NumPy's argument name
+        """Binned counts of the unmasked elements, one pass on the device
+        (pyas_hist_axes).  Each element converts to float64 as
+        ``astype(float64)`` does; bin ``i`` holds ``e[i] <= x < e[i+1]`` and the
+        last bin also ``x == e[n]``: ``np.histogram`` of the float64 selection.
+        ``bins``: an int ``n >= 1`` (edges ``np.linspace(lo, hi, n + 1)`` over
+        ``range = (lo, hi)``; ``range=None`` takes the selection's unmasked
+        min and max, ``(0, 1)`` when nothing is unmasked) or a sequence of
+        finite, strictly increasing edges.  The query returns an int64
+        ``ndarray`` of shape ``final_shape + (n_bins,)`` (never masked); with
+        ``components`` a dict of ``counts``, ``bin_edges``, ``n`` (the unmasked
+        count), ``below``, ``above`` and ``nan``.  The settings hold for one
+        query."""
+        self._hist = self._check_hist(bins, range)
+        self._method = "histogram"
+        if axis is not None:
+            self._axis = axis
+        return self
+
+    @staticmethod
+    def _check_hist(bins, range_):
+        """``{"n": bins, "edges": float64 edges or None (range=None: found by
+        the query), "uniform": evenly spaced}``.  ValueError for bad bins or
+        range (histogram.edges)."""
+        if histogram.is_count(bins):
+            if range_ is None:
+                histogram.edges(bins, (0.0, 1.0))     # the checks of the bin count
+                return {"n": int(bins), "edges": None, "uniform": True}
+            return {"n": int(bins), "edges": histogram.edges(bins, range_), "uniform": True}
+        e = histogram.edges(bins)
+        return {"n": e.size - 1, "edges": e, "uniform": False}
+
     def _set_moments(self, method, axis, ddof):
         if isinstance(ddof, (bool, np.bool_)) or not isinstance(ddof, (int, np.integer)) or ddof < 0:
             raise ValueError(f"ddof must be a non-negative int. Got {ddof!r}")
@@ -469,6 +505,7 @@ class Active:
         finally:
             self._method = None          # active.py:633
             self._weights = None         # weights are per query
+            self._hist = None            # and so are a histogram's bins
             for store in held:
                 _unhold(store)
             self._held.stores = []
@@ -483,13 +520,17 @@ class Active:
             raise ValueError(f"weights apply to mean and sum only, not to method {self._method!r}")
         if has_w and self.group is not None:
             raise NotImplementedError("weights with group=…: weighted sums are reduced on one GPU only")
+        hist = self._method == "histogram"
+        if hist and self.group is not None:
+            raise NotImplementedError("histogram with group=…: binned counts are reduced on one GPU only")
         if self._axis is None:
             self._axis = tuple(range(ds.ndim))
         elif isinstance(self._axis, int):
             self._axis = (self._axis,)
         cache_key = None
-        # (var / std and weighted queries bypass the plan cache: its plans replay pyas_partial launches)
-        if self.resident and self.group is None and self._method is not None and not second and not has_w:
+        # (var / std, weighted and histogram queries bypass the plan cache: its plans replay pyas_partial launches)
+        if self.resident and self.group is None and self._method is not None and not second and not has_w \
+                and not hist:
             ikey = _index_key(index)
             if ikey is not None:
                 cache_key = (ikey, self._norm_axes(), _missing_key(self.missing))
@@ -509,6 +550,8 @@ class Active:
                                  f"axis {i!r} drops the axis.")
         if second:
             return self._reduce_moments(indexer, compressor, filters, self._norm_axes())
+        if hist:
+            return self._reduce_hist(index, indexer, compressor, filters, self._norm_axes())
         if has_w:
             return self._reduce_weighted(indexer, compressor, filters, self._norm_axes())
         return self._reduce(indexer, compressor, filters, self._norm_axes(), cache_key)
@@ -986,6 +1029,130 @@ class Active:
         ctx.synchronize(st)
         del keep
         return self._format_moments(final.reshape(final_shape))
+
+    # -- histogram ------------------------------------------------------------------
+    def _auto_range(self, index, compressor, filters):
+        """``range=None``: the unmasked min and max of the selection as float64,
+        from a min and a max query over every axis through :meth:`_reduce` (a
+        resident variable's plan cache serves them); ``(0.0, 1.0)`` when nothing
+        is unmasked.  ValueError when either is not finite."""
+        ds = self.ds
+        saved = (self._method, self._components)
+        axes = tuple(range(ds.ndim))
+        vals = []
+        try:
+            self._components = False
+            for m in ("min", "max"):
+                self._method = m
+                res, cache_key = _MISS, None
+                if self.resident:
+                    ikey = _index_key(index)
+                    if ikey is not None:
+                        cache_key = (ikey, axes, _missing_key(self.missing))
+                        res = self._cached_query(cache_key)
+                if res is _MISS:
+                    res = self._reduce(OrthogonalIndexer(index, ds.shape, ds.chunks), compressor, filters, axes,
+                                       cache_key)
+                vals.append(res)
+        finally:
+            self._method, self._components = saved
+        if any(np.ma.getmaskarray(v).all() for v in vals):
+            return 0.0, 1.0
+        lo, hi = (float(np.asarray(np.ma.getdata(v), dtype=np.float64).reshape(-1)[0]) for v in vals)
+        if not (np.isfinite(lo) and np.isfinite(hi)):
+            raise ValueError(f"autodetected range of [{lo}, {hi}] is not finite")
+        return lo, hi
+
+    def _reduce_hist(self, index, indexer, compressor, filters, axes):
+        """histogram: every chunk adds its counts straight into the final
+        table, one int64 row of ``n_bins + 3`` slots per output
+        (pyas_hist_axes), so there are no per-chunk records and no combine.  A
+        full reduction adds into row 0; a partial one looks each chunk-local
+        output's row up in a host-built map, for box and general queries
+        alike."""
+        ds = self.ds
+        h = self._hist
+        n_bins = h["n"]
+        slots = n_bins + 3
+        final_shape = tuple(1 if i in axes else n for i, n in enumerate(indexer.shape))
+        n_final = int(np.prod(final_shape))
+        nbytes = n_final * slots * 8
+        if nbytes > histogram.TABLE_CAP_BYTES:
+            raise ValueError(f"histogram table of {n_final} outputs x ({n_bins} + 3) slots takes {nbytes} bytes, "
+                             f"above the cap of {histogram.TABLE_CAP_BYTES} bytes")
+        e = h["edges"]
+        if e is None:
+            e = histogram.edges(n_bins, self._auto_range(index, compressor, filters))
+        tab = np.zeros((n_final, slots), dtype=np.int64)
+        box = self._box_plan(indexer)
+        if box is not None:
+            dims, coords, table, pool = box
+            n = len(coords)
+        else:
+            chunk_list = list(indexer)
+            n = len(chunk_list)
+        if n == 0 or n_final == 0:
+            return self._format_hist(tab.reshape(final_shape + (slots,)), e)
+        if box is not None:
+            ctx, st, buf, offsets, fused = self._ingest(coords, compressor, filters)
+            full = _all_full(table, ds.chunks)
+            plan = ReductionPlan(ctx, ds.dtype, ds.chunks, buf.ptr, offsets, shuffle=fused,
+                                 sel_table=None if full else table, index_pool=None if full else pool,
+                                 missing=self.missing, stream=st)
+        else:
+            ctx, st, buf, offsets, fused = self._ingest([c for c, _ in chunk_list], compressor, filters)
+            sels = [self._chunk_sel(projs) for _, projs in chunk_list]
+            plan = ReductionPlan(ctx, ds.dtype, ds.chunks, buf.ptr, offsets, shuffle=fused, selections=sels,
+                                 missing=self.missing, stream=st)
+        axes_mask = 0
+        for a in axes:
+            axes_mask |= 1 << a
+        ebuf = DeviceBuffer(ctx, e.nbytes)
+        ctx.h2d(ebuf.ptr, e, st)
+        tbuf = DeviceBuffer(ctx, nbytes)
+        engine.hist_reset(ctx, tbuf.ptr, n_final, n_bins, st)
+        uniform = (e[0], n_bins / (e[-1] - e[0])) if h["uniform"] else None
+        keep = [buf, ebuf, tbuf]
+        if len(axes) == ds.ndim:
+            engine.hist_axes(ctx, plan.batch, plan.mask_up.struct, ebuf.ptr, n_bins, uniform, axes_mask, None, None,
+                             tbuf.ptr, st)
+        else:
+            # chunk-local output (C order over the kept selected dims) -> final output
+            if box is not None:
+                idx = np.indices([len(p) for p in dims]).reshape(ds.ndim, n)
+                all_projs = ([dims[d][idx[d][k]] for d in range(ds.ndim)] for k in range(n))
+            else:
+                all_projs = (projs for _, projs in chunk_list)
+            sizes, fidx = [], []
+            for projs in all_projs:
+                pos = [np.asarray(p.out_pos, dtype=np.int64) if i not in axes else np.zeros(1, dtype=np.int64)
+                       for i, p in enumerate(projs)]
+                grids = np.meshgrid(*pos, indexing="ij")
+                fidx.append(np.ravel_multi_index([x.reshape(-1) for x in grids], final_shape))
+                sizes.append(grids[0].size)
+            out_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+            meta = np.concatenate([out_off[:-1]] + fidx).astype(np.int64)
+            mbuf = DeviceBuffer(ctx, meta.nbytes)
+            ctx.h2d(mbuf.ptr, meta, st)
+            keep.append(mbuf)
+            engine.hist_axes(ctx, plan.batch, plan.mask_up.struct, ebuf.ptr, n_bins, uniform, axes_mask, mbuf.ptr,
+                             mbuf.ptr + 8 * n, tbuf.ptr, st)
+        ctx.d2h(tab, tbuf.ptr, st)
+        ctx.synchronize(st)
+        del keep
+        return self._format_hist(tab.reshape(final_shape + (slots,)), e)
+
+    def _format_hist(self, tab, e):
+        """The int64 counts of a histogram query from its table rows (counts,
+        below, above, nan), or its components."""
+        n_bins = e.size - 1
+        counts = np.ascontiguousarray(tab[..., :n_bins])
+        if self._components:
+            return {"counts": counts, "bin_edges": np.array(e, dtype=np.float64),
+                    "n": tab.sum(axis=-1), "below": np.ascontiguousarray(tab[..., n_bins]),
+                    "above": np.ascontiguousarray(tab[..., n_bins + 1]),
+                    "nan": np.ascontiguousarray(tab[..., n_bins + 2])}
+        return counts
 
     # -- weighted mean / sum ------------------------------------------------------
     def _weight_tables(self, coords):

@@ -1668,6 +1668,104 @@ int pyas_wsum_combine_grid(pyas_ctx *ctx, const pyas_wsum *in, const pyas_grid *
     return PYAS_OK;
 }
 
+int pyas_hist_axes(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask, const pyas_hist *hist,
+                   uint32_t axes_mask, const int64_t *out_offsets, const int64_t *out_index, int64_t *table,
+                   void *stream) {
+    if (!ctx) return fail(PYAS_EINVAL, "ctx is NULL");
+    if (batch && (batch->ndim < 1 || batch->ndim > PYAS_MAX_DIMS))
+        return fail(PYAS_ENOTSUP, "chunk rank %d outside 1..%d", batch->ndim, PYAS_MAX_DIMS);
+    pyas::HistArgs x;
+    std::memset(&x, 0, sizeof(x));
+    int es;
+    bool shuf, bsw, masked;
+    int rc = prepare(ctx, batch, mask, x.r, es, shuf, bsw, masked);
+    if (rc) return rc;
+    if (axes_mask >> batch->ndim) return fail(PYAS_EINVAL, "axes mask 0x%x beyond rank %d", axes_mask, batch->ndim);
+    if (!hist || !hist->edges) return fail(PYAS_EINVAL, "hist is NULL or has NULL edges");
+    if (hist->n_bins < 1 || hist->n_bins > PYAS_HIST_MAX_BINS)
+        return fail(PYAS_EINVAL, "n_bins = %d outside 1..%d", hist->n_bins, PYAS_HIST_MAX_BINS);
+    if (hist->flags & ~PYAS_HIST_UNIFORM) return fail(PYAS_EINVAL, "unknown hist flags 0x%x", hist->flags);
+    const int64_t n = batch->n_chunks;
+    if (n == 0) return PYAS_OK;
+    if (!table) return fail(PYAS_EINVAL, "table is NULL");
+    const bool full = axes_mask == (1u << batch->ndim) - 1u;
+    if (!full && !out_offsets) return fail(PYAS_EINVAL, "out_offsets is NULL");
+    PYAS_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    x.axes = axes_mask;
+    x.out_offsets = out_offsets;
+    x.out_index = out_index;
+    x.table = (unsigned long long *)table;
+    x.edges = hist->edges;
+    x.n_bins = hist->n_bins;
+    x.uniform = (hist->flags & PYAS_HIST_UNIFORM) ? 1 : 0;
+    x.lo = x.uniform ? hist->lo : 0.0;
+    x.scale = x.uniform ? hist->scale : 0.0;
+    x.bswap = bsw;
+    x.masked = masked;
+    if (full && hist->n_bins <= pyas::kHistLdsBins) {
+        // counts in LDS: a few workgroups per CU, each over a contiguous range
+        // of (chunk, tile) pairs, so a bin's global word takes one add per
+        // workgroup (PYAS_HIST_WGS: the grid's cap, read per call: tests and
+        // benches switch it; default 4 per CU)
+        const int64_t tpc = tiles_per_chunk(ctx, x.r.chunk_elems * es);
+        const int64_t pairs = n * tpc;
+        if (pairs >= (int64_t(1) << 31)) return fail(PYAS_ENOTSUP, "grid of %lld tiles", (long long)pairs);
+        const int64_t slots = (int64_t)hist->n_bins + 3;
+        int shift = 5;   // kHistMaxCopies
+        while ((1 << shift) > pyas::kHistMinCopies && (slots + 1) * 4 * (1 << shift) > pyas::kHistTabBytes) --shift;
+        const char *e = getenv("PYAS_HIST_WGS");
+        int64_t grid = e && *e ? atoll(e) : 4 * (int64_t)ctx->n_cu;
+        if (grid < 1) grid = 1;
+        if (grid > 65536) grid = 65536;
+        if (grid > pairs) grid = pairs;
+        x.bpc = tpc;
+        x.n_pairs = pairs;
+        x.shift = shift;
+        // the edges, then the copies of the row's slots and a spare one (what masked elements add to)
+        const size_t lds = (size_t)(hist->n_bins + 1) * sizeof(double) + (size_t)((slots + 1) << shift) * sizeof(uint32_t);
+        PYAS_HIP(pyas::launch_hist_full(batch->dtype, x, shuf, grid, lds, st));
+        return PYAS_OK;
+    }
+    int64_t keep_elems = 1;
+    for (int d = 0; d < batch->ndim; ++d)
+        if (!((axes_mask >> d) & 1u)) keep_elems *= batch->chunk_shape[d];
+    x.row = ((axes_mask >> (batch->ndim - 1)) & 1u) != 0;
+    int64_t bpc;
+    x.split = 1;
+    if (x.row) {
+        // a wave per 1,024 reduced positions of an output, so a chunk with few
+        // outputs still fills its workgroups
+        constexpr int64_t kWaves = pyas::kBlock / pyas::kWave;
+        const int64_t red_elems = x.r.chunk_elems / keep_elems;
+        int64_t split = (red_elems + 1023) / 1024;
+        if (split * keep_elems > 64 * kWaves) split = (64 * kWaves) / keep_elems;
+        if (split < 1) split = 1;
+        x.split = (int32_t)split;
+        bpc = (keep_elems * split + kWaves * 16 - 1) / (kWaves * 16);
+        if (split > 1) bpc = (keep_elems * split + kWaves - 1) / kWaves;
+    } else {
+        bpc = (keep_elems + pyas::kBlock - 1) / pyas::kBlock;
+    }
+    if (bpc > 64) bpc = 64;
+    if (bpc < 1) bpc = 1;
+    x.bpc = bpc;
+    const int64_t grid = n * bpc;
+    if (grid >= (int64_t(1) << 31)) return fail(PYAS_ENOTSUP, "grid too large");
+    PYAS_HIP(pyas::launch_hist_axes(batch->dtype, x, shuf, grid, st));
+    return PYAS_OK;
+}
+
+int pyas_hist_reset(pyas_ctx *ctx, int64_t *table, int64_t n_rows, int32_t n_bins, void *stream) {
+    if (!ctx) return fail(PYAS_EINVAL, "ctx is NULL");
+    if (n_rows < 0 || n_bins < 1) return fail(PYAS_EINVAL, "n_rows = %lld, n_bins = %d", (long long)n_rows, n_bins);
+    if (n_rows == 0) return PYAS_OK;
+    if (!table) return fail(PYAS_EINVAL, "table is NULL");
+    PYAS_HIP(hipSetDevice(ctx->device));
+    PYAS_HIP(hipMemsetAsync(table, 0, (size_t)n_rows * (size_t)(n_bins + 3) * sizeof(int64_t), (hipStream_t)stream));
+    return PYAS_OK;
+}
+
 int pyas_format_partials(pyas_ctx *ctx, int32_t dtype, const pyas_partial *in, int64_t n,
                          int32_t method, void *values, uint8_t *mask, int64_t *counts,
                          void *stream) {

@@ -1,0 +1,554 @@
+// pyas_hist.hip — binned counts behind Active.histogram (pyas_hist_axes of
+// include/pyas.h).
+//
+// One pass over the same bytes a mean reads.  Every unmasked selected element
+// converts to f64 as astype(float64) does and adds 1 to one slot of its
+// output's table row: n_bins counts, then below, above, nan (all int64).
+// Bin i holds e[i] <= x < e[i+1], the last bin also x == e[n].  Integers add in
+// any order, so results are exact and bit-identical from run to run.
+//
+// Bin index: a guess int(x * scale - lo * scale) clamped to [0, n-1] (uniform
+// edges; 0 otherwise), checked against e[i] and e[i+1].  A miss takes the slow
+// path: NaN / below / above / last bin, then for uniform edges up to two steps
+// of one bin, then a binary search.  Only the edge table decides, so any
+// strictly increasing edges bin correctly whatever the guess was.
+//
+// k_hist_full : every dim reduced, n_bins <= kHistLdsBins.  A capped grid; each
+//               workgroup walks a contiguous range of (chunk, tile) pairs and
+//               counts into 32-bit LDS tables with ds atomics.  The table is
+//               replicated `copies` times (slot-major, copy = thread % copies):
+//               with 32 copies the 32 lanes an LDS pass serves hit 32 banks, so
+//               a hot bin costs what a spread one does; a masked element adds
+//               to a spare slot, so the add needs no branch.  The copies are summed
+//               and added to the global int64 row (64-bit atomics, zero slots
+//               skipped) at the workgroup's end, when the output row changes,
+//               and before a copy could pass 2^32.  Whole chunks and one-run
+//               selections stream 16-B loads, register double-buffered;
+//               anything else walks per element.
+// k_hist_axes : partial axes, and every n_bins above kHistLdsBins.  Walks per
+//               element; one global 64-bit atomic add per unmasked element.
+//               Innermost dim kept: a lane per output.  Innermost dim reduced:
+//               `split` waves per output, equal slots of a wave added once.
+// Both are templated on the dtype and shuffled-or-not only; byte order, mask
+// rules and selection kind are run-time branches.
+#include <hip/hip_runtime.h>
+
+#include "pyas_kernels.hpp"   // ldg16, unpack16, unshuffle16, RadixCounter, decompose, all_masked
+
+namespace pyas {
+
+typedef unsigned long long hist_u64;
+
+// k_hist_full: at most 128 VGPRs (4 waves per SIMD; 1-byte types unpack 16 values per load and get 256), and
+// every call inlined: its six run variants put it beyond the inliner's budget, and one call left standing
+// sends the argument block to scratch
+#define PYAS_HIST_WAVES(T) __attribute__((amdgpu_waves_per_eu(sizeof(T) > 1 ? 4 : 2, 8), flatten))
+
+// largest i in [0, n-1] with e[i] <= x, given e[0] <= x < e[n]
+__device__ __forceinline__ int hist_search(const double *e, int n, double x) {
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (e[mid] <= x) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// The slot of x when the guess i (in [0, n-1]) missed.
+__device__ __forceinline__ int hist_slot_slow(const double *e, int n, bool uniform, int i, double x) {
+    if (x != x) return n + 2;
+    if (x < e[0]) return n;
+    if (x > e[n]) return n + 1;
+    if (x >= e[n - 1]) return n - 1;          // the last bin is closed: x == e[n] too
+    // e[0] <= x < e[n-1], so n >= 2 and every index below stays in [0, n-1]
+    if (uniform) {
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            if (x < e[i]) --i;
+            else if (x >= e[i + 1]) ++i;
+        }
+        if (e[i] <= x && x < e[i + 1]) return i;
+    }
+    return hist_search(e, n, x);
+}
+
+struct HistBins {
+    const double *e;       // n + 1 edges
+    int n;
+    bool uniform;
+    double scale, off;     // the guess: x * scale + off = (x - lo) * scale
+    __device__ __forceinline__ void init(const HistArgs &a, const double *edges) {
+        e = edges;
+        n = a.n_bins;
+        uniform = a.uniform != 0;
+        scale = a.scale;
+        off = -a.lo * a.scale;
+        if (!(off == off) || !uniform) {   // no guess (or lo * scale overflowed): bin 0, then the search
+            scale = 0.0;
+            off = 0.0;
+        }
+    }
+    // The slots of N values; ok[k]: x[k] is selected and unmasked (the other
+    // slots are in [0, n-1] but mean nothing).  The guesses are checked inline;
+    // the misses (rare) go one at a time through a single copy of the slow path.
+    template <int N, typename T>
+    __device__ __forceinline__ void slots(const T *x, const bool *ok, int *idx) const {
+        bool hit[N], any = false;
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+            const double xd = (double)x[k];
+            // the conversion saturates and gives 0 for NaN; whatever it gives, the index is clamped
+            int i = (int)__builtin_fma(xd, scale, off);
+            i = i < 0 ? 0 : i;
+            i = i > n - 1 ? n - 1 : i;
+            const double e0 = e[i], e1 = e[i + 1];
+            idx[k] = i;
+            hit[k] = e0 <= xd && xd < e1;
+            any |= ok[k] && !hit[k];
+        }
+        if (__builtin_expect(any, 0)) {
+            uint32_t miss = 0;
+#pragma unroll
+            for (int k = 0; k < N; ++k) miss |= (ok[k] && !hit[k]) ? 1u << k : 0u;
+            while (miss != 0) {
+                const int k = __builtin_ctz(miss);
+                miss &= miss - 1;
+                T xv = x[0];
+                int iv = idx[0];
+#pragma unroll
+                for (int j = 1; j < N; ++j) {
+                    xv = k == j ? x[j] : xv;
+                    iv = k == j ? idx[j] : iv;
+                }
+                const int s = hist_slot_slow(e, n, uniform, iv, (double)xv);
+#pragma unroll
+                for (int j = 0; j < N; ++j) idx[j] = k == j ? s : idx[j];
+            }
+        }
+    }
+};
+
+// Counts into this lane's copy of the LDS table.  A masked element adds to a
+// spare slot after the row's (never flushed), so the add needs no branch.
+struct HistLds {
+    HistBins b;
+    uint8_t *tab;          // this lane's copy of slot 0
+    int sh;                // log2(copies) + 2: byte shift of a slot
+    template <int N, typename T>
+    __device__ __forceinline__ void add(const T *x, const bool *ok) const {
+        int idx[N];
+        b.template slots<N>(x, ok, idx);
+        const int spare = b.n + 3;
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+            const uint32_t s = (uint32_t)(ok[k] ? idx[k] : spare);
+            __hip_atomic_fetch_add(reinterpret_cast<uint32_t *>(tab + (s << sh)), 1u, __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+    }
+    // N values under mask mode M (0 none, kMaskRange, kMaskAll)
+    template <int N, int M, typename T>
+    __device__ __forceinline__ void add_n(const T *x, const MaskT<T> &mk) const {
+        bool ok[N];
+#pragma unroll
+        for (int k = 0; k < N; ++k) ok[k] = M ? !mk.template masked_m<M>(x[k]) : true;
+        add<N>(x, ok);
+    }
+};
+
+// one global atomic per element (a lane per output)
+struct HistLane {
+    HistBins b;
+    hist_u64 *row;
+    template <int N, typename T>
+    __device__ __forceinline__ void add(const T *x, const bool *ok) const {
+        int idx[N];
+        b.template slots<N>(x, ok, idx);
+#pragma unroll
+        for (int k = 0; k < N; ++k)
+            if (ok[k]) __hip_atomic_fetch_add(row + idx[k], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+};
+
+// every active lane of the wave adds to the same row: equal slots add once
+struct HistWave {
+    HistBins b;
+    hist_u64 *row;
+    template <int N, typename T>
+    __device__ __forceinline__ void add(const T *x, const bool *ok) const {
+        int idx[N];
+        b.template slots<N>(x, ok, idx);
+        const int lane = threadIdx.x & (kWave - 1);
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+            uint64_t rem = __ballot(ok[k]);
+            while (rem) {
+                const int leader = __builtin_ctzll(rem);
+                const int sl = __shfl(idx[k], leader);
+                const uint64_t m = __ballot(ok[k] && idx[k] == sl);
+                if (lane == leader)
+                    __hip_atomic_fetch_add(row + sl, (hist_u64)__builtin_popcountll(m), __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_AGENT);
+                rem &= ~m;
+            }
+        }
+    }
+};
+
+// ---------------------------------------------------------------------------
+// contiguous runs (the layout of mom_run_plain / mom_run_shuffled)
+// ---------------------------------------------------------------------------
+template <typename T, bool BSWAP, int M>
+__device__ __forceinline__ void hist_run_plain(const uint8_t *base, int64_t m0, int64_t m1, const HistLds &acc, const MaskT<T> &mk) {
+    constexpr int ES = sizeof(T);
+    constexpr int N = 16 / ES;
+    const int tid = threadIdx.x;
+    const int64_t b0 = m0 * ES, b1 = m1 * ES;               // byte range in the chunk
+    const int64_t mis = (int64_t)((uintptr_t)base & 15);
+    const int64_t a0 = ((b0 + mis + 15) & ~(int64_t)15) - mis;  // first 16-B aligned byte
+    const int64_t a1 = ((b1 + mis) & ~(int64_t)15) - mis;
+    if (a0 >= a1) {
+        for (int64_t i = m0 + tid; i < m1; i += kBlock) {
+            const T v = load_plain<T, BSWAP>(base, i);
+            acc.template add_n<1, M>(&v, mk);
+        }
+        return;
+    }
+    const int64_t nhead = (a0 - b0) / ES, ntail = (b1 - a1) / ES;
+    if (tid < nhead) {
+        const T v = load_plain<T, BSWAP>(base, m0 + tid);
+        acc.template add_n<1, M>(&v, mk);
+    }
+    if (tid < ntail) {
+        const T v = load_plain<T, BSWAP>(base, m1 - ntail + tid);
+        acc.template add_n<1, M>(&v, mk);
+    }
+    const uint4 *v = reinterpret_cast<const uint4 *>(base + a0);
+    const int64_t nvec = (a1 - a0) / 16;
+    constexpr int U = 4;
+    constexpr int64_t STEP = (int64_t)U * kBlock;
+    const int64_t nsteps = nvec / STEP;
+    auto consume = [&](const uint4 *r) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            T x[N];
+            unpack16<T, BSWAP>(r[u], x);
+            acc.template add_n<N, M>(x, mk);
+        }
+    };
+    if (nsteps > 0) {
+        uint4 cur[U], nxt[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) cur[u] = ldg16(v + tid + u * kBlock);
+        for (int64_t s = 0; s + 1 < nsteps; ++s) {
+            // the next step's loads are in flight while this step is binned
+#pragma unroll
+            for (int u = 0; u < U; ++u) nxt[u] = ldg16(v + (s + 1) * STEP + tid + u * kBlock);
+            consume(cur);
+#pragma unroll
+            for (int u = 0; u < U; ++u) cur[u] = nxt[u];
+        }
+        consume(cur);
+    }
+    for (int64_t k = nsteps * STEP + tid; k < nvec; k += kBlock) {
+        T x[N];
+        unpack16<T, BSWAP>(ldg16(v + k), x);
+        acc.template add_n<N, M>(x, mk);
+    }
+}
+
+// Shuffled layout, chunk elements [i0, i1); n = elements in the chunk.
+template <typename T, bool BSWAP, int M>
+__device__ __forceinline__ void hist_run_shuffled(const uint8_t *base, int64_t n, int64_t i0, int64_t i1, const HistLds &acc,
+                                  const MaskT<T> &mk) {
+    constexpr int ES = sizeof(T);
+    const int tid = threadIdx.x;
+    const bool vec_ok = (((uintptr_t)base & 15) == 0) && ((n & 15) == 0);
+    const int64_t g0 = (i0 + 15) & ~(int64_t)15, g1 = i1 & ~(int64_t)15;
+    if (!vec_ok || g0 >= g1) {
+        for (int64_t i = i0 + tid; i < i1; i += kBlock) {
+            const T v = load_shuffled<T, BSWAP>(base, n, i);
+            acc.template add_n<1, M>(&v, mk);
+        }
+        return;
+    }
+    if (tid < g0 - i0) {
+        const T v = load_shuffled<T, BSWAP>(base, n, i0 + tid);
+        acc.template add_n<1, M>(&v, mk);
+    }
+    if (tid < i1 - g1) {
+        const T v = load_shuffled<T, BSWAP>(base, n, g1 + tid);
+        acc.template add_n<1, M>(&v, mk);
+    }
+    const int64_t ng = (g1 - g0) / 16;
+    for (int64_t g = tid; g < ng; g += kBlock) {
+        const int64_t i = g0 + g * 16;
+        uint4 pl[ES];
+#pragma unroll
+        for (int b = 0; b < ES; ++b) pl[b] = ldg16(reinterpret_cast<const uint4 *>(base + (int64_t)b * n + i));
+        T x[16];
+        unshuffle16<T, BSWAP>(pl, x);
+        acc.template add_n<16, M>(x, mk);
+    }
+}
+
+template <typename T, bool SHUF, bool BSWAP>
+__device__ __forceinline__ void hist_run(int mode, const uint8_t *base, int64_t n, int64_t i0, int64_t i1,
+                                         const HistLds &acc, const MaskT<T> &mk) {
+    if constexpr (SHUF && sizeof(T) > 1) {
+        if (mode == 0) hist_run_shuffled<T, BSWAP, 0>(base, n, i0, i1, acc, mk);
+        else if (mode == kMaskRange) hist_run_shuffled<T, BSWAP, kMaskRange>(base, n, i0, i1, acc, mk);
+        else hist_run_shuffled<T, BSWAP, kMaskAll>(base, n, i0, i1, acc, mk);
+    } else {
+        if (mode == 0) hist_run_plain<T, BSWAP, 0>(base, i0, i1, acc, mk);
+        else if (mode == kMaskRange) hist_run_plain<T, BSWAP, kMaskRange>(base, i0, i1, acc, mk);
+        else hist_run_plain<T, BSWAP, kMaskAll>(base, i0, i1, acc, mk);
+    }
+}
+
+template <typename T, bool SHUF>
+__device__ __forceinline__ T hist_load(const uint8_t *base, int64_t n, int64_t i, bool bsw) {
+    return bsw ? load_elem<T, SHUF, true>(base, n, i) : load_elem<T, SHUF, false>(base, n, i);
+}
+
+// Per-element walk of positions q0, q0 + stride, ... < n_pos over the dims in
+// `dmask` (rc: the radix counter at q0), 4 loads in flight.
+template <typename T, bool SHUF, typename Acc>
+__device__ __forceinline__ void hist_walk(const ReduceArgs &r, const uint8_t *base, const Sel &s, uint32_t dmask,
+                                          const Decomp &base_o, RadixCounter &rc, int64_t q0, int64_t n_pos,
+                                          int64_t stride, bool bsw, const MaskT<T> &mk, const Acc &acc) {
+    constexpr int U = 4;
+    int64_t q = q0;
+    for (; q + (U - 1) * stride < n_pos; q += U * stride) {
+        Decomp od[U];
+        T x[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            od[u] = base_o;
+            rc.locate(s, r.pool, r.cstride, r.tab, r.ndim, dmask, od[u]);
+            rc.advance();
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) x[u] = hist_load<T, SHUF>(base, r.chunk_elems, od[u].mem, bsw);
+        bool ok[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) ok[u] = !all_masked(mk, r.tab, od[u], x[u]);
+        acc.template add<U>(x, ok);
+    }
+    for (; q < n_pos; q += stride) {
+        Decomp od = base_o;
+        rc.locate(s, r.pool, r.cstride, r.tab, r.ndim, dmask, od);
+        rc.advance();
+        const T x = hist_load<T, SHUF>(base, r.chunk_elems, od.mem, bsw);
+        const bool ok = !all_masked(mk, r.tab, od, x);
+        acc.template add<1>(&x, &ok);
+    }
+}
+
+__device__ __forceinline__ int64_t hist_row(const HistArgs &a, int64_t c, int64_t o) {
+    if (!a.out_offsets) return 0;   // every dim reduced, one output
+    const int64_t k = a.out_offsets[c] + o;
+    return a.out_index ? a.out_index[k] : k;
+}
+
+// Sum the copies of every slot into the global row and leave the LDS table
+// zero.  Every thread of the workgroup calls it.
+__device__ __forceinline__ void hist_flush(uint32_t *tab, int slots, int shift, hist_u64 *row) {
+    __syncthreads();
+    const int copies = 1 << shift;
+    for (int s = threadIdx.x; s < slots; s += kBlock) {
+        hist_u64 sum = 0;
+        for (int k = 0; k < copies; ++k) {
+            uint32_t *p = tab + (s << shift) + ((k + threadIdx.x) & (copies - 1));   // lanes on different banks
+            sum += *p;
+            *p = 0;
+        }
+        if (sum) __hip_atomic_fetch_add(row + s, sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+}
+
+// ---------------------------------------------------------------------------
+// every dim reduced: workgroup g walks pairs [g P / G, (g + 1) P / G), pair =
+// tile t of chunk c
+// ---------------------------------------------------------------------------
+template <typename T, bool SHUF>
+__global__ __launch_bounds__(kBlock) PYAS_HIST_WAVES(T) void k_hist_full(HistArgs a) {
+    extern __shared__ double s_hist[];   // n_bins + 1 edges, then (slots + 1 spare) * copies counts
+    const ReduceArgs &r = a.r;
+    const int n = a.n_bins, slots = n + 3, shift = a.shift;
+    double *s_e = s_hist;
+    uint32_t *s_tab = reinterpret_cast<uint32_t *>(s_hist + n + 1);
+    for (int k = threadIdx.x; k <= n; k += kBlock) s_e[k] = a.edges[k];
+    for (int k = threadIdx.x; k < ((slots + 1) << shift); k += kBlock) s_tab[k] = 0;
+    __syncthreads();
+    HistLds acc;
+    acc.b.init(a, s_e);
+    acc.tab = reinterpret_cast<uint8_t *>(s_tab + (threadIdx.x & ((1 << shift) - 1)));
+    acc.sh = shift + 2;
+    MaskT<T> mk;
+    mk.init(r.mask);
+    const bool tabs = r.tab.on[0] || r.tab.on[1];
+    const int64_t p0 = (int64_t)blockIdx.x * a.n_pairs / gridDim.x;
+    const int64_t p1 = ((int64_t)blockIdx.x + 1) * a.n_pairs / gridDim.x;
+    int64_t cur_row = 0;
+    uint64_t pending = 0;   // elements handed to the LDS table since its last flush
+    for (int64_t p = p0; p < p1; ++p) {
+        const int64_t c = p / a.bpc, t = p % a.bpc;
+        const uint8_t *base = r.data + r.offsets[c];
+        Sel s;
+        load_sel(s, r.sel, c, r.ndim, r.shape);
+        // One contiguous run?  From the innermost dim: whole dims, then one
+        // unit-step range, then single indices.
+        int64_t total = 1, m0 = 0;
+        bool contig = !tabs, inner_full = true;
+#pragma unroll
+        for (int d = PYAS_MAX_DIMS - 1; d >= 0; --d) {
+            if (d < r.ndim) {
+                const int64_t cnt = s.cnt[d];
+                total *= cnt;
+                if (s.step[d] == 0) contig = false;
+                if (cnt != 1 && (!inner_full || s.step[d] != 1)) contig = false;
+                m0 += (int64_t)s.start[d] * r.cstride[d];
+                if (!(s.start[d] == 0 && s.step[d] == 1 && cnt == r.shape[d])) inner_full = false;
+            }
+        }
+        // this tile's share of the selection: whole 16-element groups
+        const int64_t per = (((total + a.bpc - 1) / a.bpc) + 15) & ~(int64_t)15;
+        const int64_t e0 = t * per < total ? t * per : total;
+        const int64_t e1 = e0 + per < total ? e0 + per : total;
+        if (e0 >= e1) continue;
+        const int64_t row = hist_row(a, c, 0);
+        // a copy's count is at most `pending` (< 2^31 per pair): flush before it could wrap
+        if (pending && (row != cur_row || pending + (uint64_t)(e1 - e0) > 0xFFFFFFFFull)) {
+            hist_flush(s_tab, slots, shift, a.table + cur_row * slots);
+            pending = 0;
+        }
+        cur_row = row;
+        pending += (uint64_t)(e1 - e0);
+        if (contig) {
+            const uint32_t f = r.mask.flags;
+            const int mode = !a.masked || f == 0 ? 0 : (f & (PYAS_MASK_EQ0 | PYAS_MASK_EQ1)) ? kMaskAll : kMaskRange;
+            if (a.bswap) hist_run<T, SHUF, true>(mode, base, r.chunk_elems, m0 + e0, m0 + e1, acc, mk);
+            else hist_run<T, SHUF, false>(mode, base, r.chunk_elems, m0 + e0, m0 + e1, acc, mk);
+        } else if (e0 + threadIdx.x < e1) {
+            const uint32_t all = (1u << r.ndim) - 1u;
+            RadixCounter rc;
+            rc.init(s, r.ndim, all, (uint64_t)(e0 + threadIdx.x), (uint64_t)kBlock);
+            const Decomp zero{0, {0, 0}};
+            hist_walk<T, SHUF>(r, base, s, all, zero, rc, e0 + threadIdx.x, e1, kBlock, a.bswap, mk, acc);
+        }
+    }
+    if (pending) hist_flush(s_tab, slots, shift, a.table + cur_row * slots);
+}
+
+// ---------------------------------------------------------------------------
+// partial axes and the generic form: global atomics into
+// table[row(c, o) * slots + slot], o in C order over the kept selected dims
+// ---------------------------------------------------------------------------
+template <typename T, bool SHUF>
+__global__ __launch_bounds__(kBlock) void k_hist_axes(HistArgs a) {
+    const ReduceArgs &r = a.r;
+    const int64_t c = (int64_t)blockIdx.x / a.bpc, b = (int64_t)blockIdx.x % a.bpc;
+    const uint8_t *base = r.data + r.offsets[c];
+    const int64_t slots = (int64_t)a.n_bins + 3;
+    // the edges from LDS when they fit
+    __shared__ double s_e[kHistLdsBins + 1];
+    const double *e = a.edges;
+    if (a.n_bins <= kHistLdsBins) {   // uniform
+        for (int k = threadIdx.x; k <= a.n_bins; k += kBlock) s_e[k] = a.edges[k];
+        __syncthreads();
+        e = s_e;
+    }
+    HistBins bins;
+    bins.init(a, e);
+    Sel s;
+    load_sel(s, r.sel, c, r.ndim, r.shape);
+    MaskT<T> mk;
+    mk.init(r.mask);
+    const uint32_t red = a.axes, keep = ~a.axes & ((1u << r.ndim) - 1u);
+    int64_t n_keep = 1, n_red = 1;
+#pragma unroll
+    for (int d = 0; d < PYAS_MAX_DIMS; ++d) {
+        if (d < r.ndim) {
+            if ((red >> d) & 1u) n_red *= s.cnt[d];
+            else n_keep *= s.cnt[d];
+        }
+    }
+    if (n_red <= 0) return;
+    if (!a.row) {   // a lane per output
+        for (int64_t o = b * kBlock + threadIdx.x; o < n_keep; o += a.bpc * kBlock) {
+            Decomp bo{0, {0, 0}};
+            decompose(s, r.pool, r.cstride, r.tab, r.ndim, keep, o, bo);
+            RadixCounter rc;
+            rc.init(s, r.ndim, red, 0, 1);
+            const HistLane acc{bins, a.table + hist_row(a, c, o) * slots};
+            hist_walk<T, SHUF>(r, base, s, red, bo, rc, 0, n_red, 1, a.bswap, mk, acc);
+        }
+    } else {        // `split` waves per output: wave part takes positions part * 64 + lane, + split * 64, ...
+        constexpr int kWaves = kBlock / kWave;
+        const int lane = threadIdx.x & (kWave - 1);
+        const int64_t split = a.split;
+        for (int64_t u = b * kWaves + threadIdx.x / kWave; u < n_keep * split; u += a.bpc * kWaves) {
+            const int64_t o = u / split, q0 = (u % split) * kWave + lane;
+            if (q0 < n_red) {
+                Decomp bo{0, {0, 0}};
+                decompose(s, r.pool, r.cstride, r.tab, r.ndim, keep, o, bo);
+                RadixCounter rc;
+                rc.init(s, r.ndim, red, (uint64_t)q0, (uint64_t)(split * kWave));
+                const HistWave acc{bins, a.table + hist_row(a, c, o) * slots};
+                hist_walk<T, SHUF>(r, base, s, red, bo, rc, q0, n_red, split * kWave, a.bswap, mk, acc);
+            }
+        }
+    }
+}
+
+template <typename T>
+hipError_t launch_hist_full_t(const HistArgs &a, bool shuf, int64_t grid, size_t lds, hipStream_t st) {
+    if constexpr (sizeof(T) > 1) {
+        if (shuf) {
+            hipLaunchKernelGGL((k_hist_full<T, true>), dim3((unsigned)grid), dim3(kBlock), lds, st, a);
+            return hipGetLastError();
+        }
+    }
+    hipLaunchKernelGGL((k_hist_full<T, false>), dim3((unsigned)grid), dim3(kBlock), lds, st, a);
+    return hipGetLastError();
+}
+
+template <typename T>
+hipError_t launch_hist_axes_t(const HistArgs &a, bool shuf, int64_t grid, hipStream_t st) {
+    if constexpr (sizeof(T) > 1) {
+        if (shuf) {
+            hipLaunchKernelGGL((k_hist_axes<T, true>), dim3((unsigned)grid), dim3(kBlock), 0, st, a);
+            return hipGetLastError();
+        }
+    }
+    hipLaunchKernelGGL((k_hist_axes<T, false>), dim3((unsigned)grid), dim3(kBlock), 0, st, a);
+    return hipGetLastError();
+}
+
+#define PYAS_HIST_DISPATCH(FN, ...)                                  \
+    switch (dtype) {                                                 \
+        case PYAS_I8: return FN<int8_t>(__VA_ARGS__);                \
+        case PYAS_U8: return FN<uint8_t>(__VA_ARGS__);               \
+        case PYAS_I16: return FN<int16_t>(__VA_ARGS__);              \
+        case PYAS_U16: return FN<uint16_t>(__VA_ARGS__);             \
+        case PYAS_I32: return FN<int32_t>(__VA_ARGS__);              \
+        case PYAS_U32: return FN<uint32_t>(__VA_ARGS__);             \
+        case PYAS_I64: return FN<int64_t>(__VA_ARGS__);              \
+        case PYAS_U64: return FN<uint64_t>(__VA_ARGS__);             \
+        case PYAS_F32: return FN<float>(__VA_ARGS__);                \
+        case PYAS_F64: return FN<double>(__VA_ARGS__);               \
+        default: return hipErrorInvalidValue;                        \
+    }
+
+hipError_t launch_hist_full(int dtype, const HistArgs &a, bool shuf, int64_t grid, size_t lds, hipStream_t st) {
+    PYAS_HIST_DISPATCH(launch_hist_full_t, a, shuf, grid, lds, st)
+}
+
+hipError_t launch_hist_axes(int dtype, const HistArgs &a, bool shuf, int64_t grid, hipStream_t st) {
+    PYAS_HIST_DISPATCH(launch_hist_axes_t, a, shuf, grid, st)
+}
+
+}  // namespace pyas

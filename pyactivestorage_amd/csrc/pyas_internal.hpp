@@ -295,6 +295,29 @@ hipError_t launch_wsum_segments(const pyas_wsum *in, const int64_t *index, const
                                 pyas_wsum *out, hipStream_t st);
 hipError_t launch_wsum_grid(const pyas_wsum *in, const pyas_grid &g, int64_t n_out, int64_t n_layers,
                             pyas_wsum *out, hipStream_t st);
+// binned counts (pyas_hist.hip): int64 table rows of n_bins + 3 slots
+constexpr int kHistLdsBins = 2048;    // most bins of the LDS form (k_hist_full) and of LDS-staged edges
+constexpr int kHistMaxCopies = 32;    // k_hist_full: most copies of its LDS table (one per lane of an LDS pass)
+constexpr int kHistMinCopies = 4;     //              fewest (one per wave)
+constexpr int kHistTabBytes = 16384;  //              copies halve until the tables fit this (or reach the fewest)
+struct HistArgs {
+    ReduceArgs r;                     // r.out unused
+    uint32_t axes;                    // reduced dims
+    int64_t bpc;                      // k_hist_axes: workgroups per chunk; k_hist_full: tiles per chunk
+    int64_t n_pairs;                  // k_hist_full: n_chunks * bpc (chunk, tile) pairs, shared out over the grid
+    const int64_t *out_offsets;       // NULL (every dim reduced): row 0
+    const int64_t *out_index;         // NULL: the identity
+    unsigned long long *table;
+    const double *edges;              // pyas_hist
+    int32_t n_bins, uniform;
+    double lo, scale;
+    int32_t shift;                    // k_hist_full: log2 of the LDS table's copies
+    int32_t split;                    // k_hist_axes, innermost dim reduced: waves per output
+    bool bswap, masked;
+    bool row;                         // innermost dim reduced
+};
+hipError_t launch_hist_full(int dtype, const HistArgs &a, bool shuf, int64_t grid, size_t lds, hipStream_t st);
+hipError_t launch_hist_axes(int dtype, const HistArgs &a, bool shuf, int64_t grid, hipStream_t st);
 // host ingest (pyas_ingest.hip): pread ring -> pinned slots -> H2D
 struct Ingest;
 Ingest *ingest_create(int device);

@@ -238,6 +238,27 @@ def moments_combine_grid(ctx: Context, in_ptr, grid: _lib.Grid, out_ptr, stream)
                "pyas_moments_combine_grid")
 
 
+def hist_axes(ctx: Context, batch: _lib.Batch, mask: _lib.Mask, edges_ptr, n_bins: int, uniform, axes_mask: int,
+              out_offsets_ptr, out_index_ptr, table_ptr, stream) -> None:
+    """pyas_hist_axes: binned counts added into int64 table rows of
+    ``n_bins + 3`` slots (counts, below, above, nan).  ``edges_ptr``: the
+    ``n_bins + 1`` float64 edges on the device; ``uniform``: None, or the
+    ``(lo, scale)`` of the kernels' first guess for evenly spaced edges.
+    ``out_offsets_ptr`` may be None with every dim in ``axes_mask`` (row 0);
+    ``out_index_ptr`` None is the identity."""
+    h = _lib.Hist(edges_ptr, int(n_bins), 0, 0.0, 0.0)
+    if uniform is not None:
+        h.flags, h.lo, h.scale = _lib.HIST_UNIFORM, float(uniform[0]), float(uniform[1])
+    _lib.check(ctx.lib.pyas_hist_axes(ctx.handle, ctypes.byref(batch), ctypes.byref(mask), ctypes.byref(h),
+                                      int(axes_mask), out_offsets_ptr, out_index_ptr, table_ptr, stream),
+               "pyas_hist_axes")
+
+
+def hist_reset(ctx: Context, table_ptr, n_rows: int, n_bins: int, stream) -> None:
+    """pyas_hist_reset: zero ``n_rows`` table rows on the stream."""
+    _lib.check(ctx.lib.pyas_hist_reset(ctx.handle, table_ptr, int(n_rows), int(n_bins), stream), "pyas_hist_reset")
+
+
 def wsum_axes(ctx: Context, batch: _lib.Batch, mask: _lib.Mask, pool_ptr, origin_ptr, axes_mask: int,
               out_offsets_ptr, out_ptr, stream) -> None:
     """pyas_wsum_axes: count / sum w / sum w x records per chunk output, laid
