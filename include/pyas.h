@@ -626,6 +626,58 @@ int pyas_hist_axes(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask
 /* Zero n_rows table rows of n_bins + 3 int64 on the stream. */
 int pyas_hist_reset(pyas_ctx *ctx, int64_t *table, int64_t n_rows, int32_t n_bins, void *stream);
 
+/* ---- exact order statistics (Active.quantile) --------------------------------
+ * The k-th smallest unmasked selected element of every output, by a radix
+ * select over keys, most significant digit first.
+ * Key rule: every element maps to an unsigned key in the order of the values;
+ * a caller inverts it to read the element back.
+ *   u8, u16, u32   32-bit key: the value, zero-extended.
+ *   i8, i16, i32   32-bit key: the value sign-extended to 32 bits, sign bit
+ *                  flipped (key ^ 0x80000000 is the value).
+ *   u64 / i64      64-bit key: the value / the value with its sign bit flipped.
+ *   f32 / f64      32- / 64-bit key: add 0 (so -0.0 becomes +0.0), take the
+ *                  bits u; if the sign bit is set the key is ~u, otherwise
+ *                  u | sign.  Back: key & sign ? key ^ sign : ~key.
+ *                  NaN has no key: it counts in `nan`, decided on the value.
+ * A pass counts one digit: `bits` bits (1..PYAS_SELECT_MAX_BITS) at `shift`.
+ * Table row of one output: 2^bits digit counts, then below, above, nan: the
+ * histogram's row of 2^bits + 3 int64, zeroed by pyas_hist_reset(n_bins =
+ * 2^bits).  With hi = key >> (shift + bits) (0 when the digit is the key's
+ * first), an element adds 1 to slot (key >> shift) & (2^bits - 1) when hi ==
+ * prefix[row], to `below` when hi < prefix[row], to `above` when hi >
+ * prefix[row].  On every pass counts + below + above + nan is the row's
+ * unmasked element count.  pyas_select_step then extends each row's prefix by
+ * the digit that holds its rank; after the last digit (shift 0) prefix[row] is
+ * the key of the row's rank-th smallest element. */
+#define PYAS_SELECT_MAX_BITS 11
+typedef struct {
+    const uint64_t *prefix;  /* device, one per table row; NULL on the first pass (every prefix 0) */
+    int32_t shift;           /* the digit's lowest bit; shift + bits <= the key's width */
+    int32_t bits;            /* 1..PYAS_SELECT_MAX_BITS */
+} pyas_select;
+
+/* pyas_hist_axes with the digit rule (same argument checks, row mapping and
+ * errors): with every dim in axes_mask the counts go through LDS into row 0 and
+ * prefix[0] is the one prefix.  PYAS_EINVAL when select or table is NULL, bits
+ * or shift is out of range, or prefix is NULL below the first digit. */
+int pyas_select_axes(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask,
+                     const pyas_select *select, uint32_t axes_mask, const int64_t *out_offsets,
+                     const int64_t *out_index, int64_t *table, void *stream);
+/* Between passes, one wave per row (all pointers device): the running count
+ * starts at the row's `below`, plus below_base[row] when below_base is not
+ * NULL; the first digit j at which it exceeds rank[row] (zero-based, among the
+ * row's non-NaN elements) gives prefix[row] = (prefix[row] << bits) | j.  A row
+ * whose digit counts are all zero keeps its prefix.  The caller zeroes prefix
+ * before the first pass. */
+int pyas_select_step(pyas_ctx *ctx, const int64_t *table, int64_t n_rows, int32_t bits,
+                     const int64_t *rank, uint64_t *prefix, const int64_t *below_base, void *stream);
+/* One wave per row (device pointers): totals[2 row] = the sum of the row's
+ * 2^bits + 3 slots (its unmasked elements, NaN included), totals[2 row + 1] =
+ * its nan slot.  What a caller needs of a pass's table to set the ranks,
+ * without copying the table. */
+int pyas_select_totals(pyas_ctx *ctx, const int64_t *table, int64_t n_rows, int32_t bits,
+                       int64_t *totals, void *stream);
+
 /* Result formatting on the device: the last step of Active._from_storage
  * (active.py:591-630) applied to n combined partials (device), so that only
  * the result's values and mask cross PCIe (9-16 bytes per output instead of

@@ -64,6 +64,14 @@ HIST_UNIFORM = 1
 HIST_MAX_BINS = 1 << 20
 
 
+class Select(ctypes.Structure):
+    """pyas_select: the device prefixes (one per table row, NULL on the first pass) and the digit of a pass."""
+    _fields_ = [("prefix", ctypes.c_void_p), ("shift", ctypes.c_int32), ("bits", ctypes.c_int32)]
+
+
+SELECT_MAX_BITS = 11
+
+
 class Mask(ctypes.Structure):
     _fields_ = [
         ("flags", ctypes.c_uint32),
@@ -237,6 +245,10 @@ SIGNATURES = {
     "pyas_hist_axes": [_vp, ctypes.POINTER(Batch), ctypes.POINTER(Mask), ctypes.POINTER(Hist), _u32, _vp, _vp, _vp,
                        _vp],
     "pyas_hist_reset": [_vp, _vp, _i64, _i32, _vp],
+    "pyas_select_axes": [_vp, ctypes.POINTER(Batch), ctypes.POINTER(Mask), ctypes.POINTER(Select), _u32, _vp, _vp,
+                         _vp, _vp],
+    "pyas_select_step": [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp],
+    "pyas_select_totals": [_vp, _vp, _i64, _i32, _vp, _vp],
     "pyas_format_partials": [_vp, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _vp],
     "pyas_unshuffle": [_vp, _vp, _vp, _i64, _i32, _vp],
     "pyas_unshuffle_chunks": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp],

@@ -30,9 +30,12 @@ count / mean / m2 records (``pyas_moments_axes``) merged with Chan's formula
 in the order the sums are combined in (``_reduce_moments``);
 ``.mean(axis, weights={dim: vector})`` / ``.sum(axis, weights=...)``, count /
 sum w / sum w x records (``pyas_wsum_axes``) merged by addition
-(``_reduce_weighted``); and ``.histogram(bins, range, axis)``, int64 counts
+(``_reduce_weighted``); ``.histogram(bins, range, axis)``, int64 counts
 added by every chunk straight into the result table (``pyas_hist_axes``,
-``_reduce_hist``).
+``_reduce_hist``); and ``.quantile(q, axis, method)`` / ``.median(axis)``,
+exact order statistics by a radix select over keys, a few passes of digit
+counts in the histogram's table (``pyas_select_axes``, ``pyas_select_step``,
+``_reduce_select``).
 """
 from __future__ import annotations
 
@@ -44,7 +47,7 @@ import warnings
 
 import numpy as np
 
-from . import _lib, engine, histogram, moments, selection, weighted, zerosign
+from . import _lib, engine, histogram, moments, quantile, selection, weighted, zerosign
 from .batch import ReductionPlan, _all_full
 from .device import DeviceBuffer, get_context
 from .dtypes import native, sum_dtype
@@ -327,6 +330,8 @@ class Active:
         self._ddof = 0                  # var / std: the divisor is count - ddof
         self._weights = None            # mean / sum: {dim: float64 vector} of the next query
         self._hist = None               # histogram: the bins of the next query (_check_hist)
+        self._quant = None              # quantile: {"q": float64 (0-D or 1-D), "method": str} of the next query
+        self._select_stats = None       # the last quantile query: its digit width, count launches and chains
         self._max_threads = int(max_threads)
         self.device = device
         # f3: zlib chunks inflate on the GPU (True), on the host reader threads
@@ -368,6 +373,7 @@ class Active:
         self._ddof = 0
         self._weights = None
         self._hist = None
+        self._quant = None
 
     @property
     def weights(self):
@@ -473,6 +479,29 @@ class Active:
             self._axis = axis
         return self
 
+    def quantile(self, q, axis=None, method="linear"):
+        """Exact quantiles of the unmasked elements: per output
+        ``np.quantile(x64, q, method=method)`` of the float64 copy ``x64`` of
+        its unmasked selected elements, found on the device by a radix select
+        over order-preserving keys (pyas_select_axes / pyas_select_step), so
+        no element is sorted or copied.  ``q``: a scalar or 1-D sequence in
+        [0, 1]; ``method``: ``linear``, ``lower``, ``higher``, ``midpoint`` or
+        ``nearest``, with NumPy's meaning.  The query returns a float64 masked
+        array of shape ``final_shape + q.shape``: masked where an output has
+        no unmasked element, NaN where any of its unmasked elements is NaN.
+        With ``components`` a dict of ``quantile``, ``n`` (int64: the unmasked
+        elements per output, NaNs included) and ``nan`` (int64).  The sign of
+        a zero result is not specified.  The settings hold for one query."""
+        self._quant = {"q": quantile.check_q(q), "method": quantile.check_method(method)}
+        self._method = "quantile"
+        if axis is not None:
+            self._axis = axis
+        return self
+
+    def median(self, axis=None):
+        """The median of the unmasked elements: :meth:`quantile` at 0.5."""
+        return self.quantile(0.5, axis=axis)
+
     @staticmethod
     def _check_hist(bins, range_):
         """``{"n": bins, "edges": float64 edges or None (range=None: found by
@@ -506,6 +535,7 @@ class Active:
             self._method = None          # active.py:633
             self._weights = None         # weights are per query
             self._hist = None            # and so are a histogram's bins
+            self._quant = None           # and a quantile's q and method
             for store in held:
                 _unhold(store)
             self._held.stores = []
@@ -523,14 +553,18 @@ class Active:
         hist = self._method == "histogram"
         if hist and self.group is not None:
             raise NotImplementedError("histogram with group=…: binned counts are reduced on one GPU only")
+        quant = self._method == "quantile"
+        if quant and self.group is not None:
+            raise NotImplementedError("quantile with group=…: order statistics are selected on one GPU only")
         if self._axis is None:
             self._axis = tuple(range(ds.ndim))
         elif isinstance(self._axis, int):
             self._axis = (self._axis,)
         cache_key = None
-        # (var / std, weighted and histogram queries bypass the plan cache: its plans replay pyas_partial launches)
+        # (var / std, weighted, histogram and quantile queries bypass the plan cache: its plans replay pyas_partial
+        # launches)
         if self.resident and self.group is None and self._method is not None and not second and not has_w \
-                and not hist:
+                and not hist and not quant:
             ikey = _index_key(index)
             if ikey is not None:
                 cache_key = (ikey, self._norm_axes(), _missing_key(self.missing))
@@ -552,6 +586,8 @@ class Active:
             return self._reduce_moments(indexer, compressor, filters, self._norm_axes())
         if hist:
             return self._reduce_hist(index, indexer, compressor, filters, self._norm_axes())
+        if quant:
+            return self._reduce_select(indexer, compressor, filters, self._norm_axes())
         if has_w:
             return self._reduce_weighted(indexer, compressor, filters, self._norm_axes())
         return self._reduce(indexer, compressor, filters, self._norm_axes(), cache_key)
@@ -1070,7 +1106,6 @@ class Active:
         full reduction adds into row 0; a partial one looks each chunk-local
         output's row up in a host-built map, for box and general queries
         alike."""
-        ds = self.ds
         h = self._hist
         n_bins = h["n"]
         slots = n_bins + 3
@@ -1084,6 +1119,32 @@ class Active:
         if e is None:
             e = histogram.edges(n_bins, self._auto_range(index, compressor, filters))
         tab = np.zeros((n_final, slots), dtype=np.int64)
+        cp = self._count_plan(indexer, compressor, filters, axes, final_shape)
+        if cp is None:
+            return self._format_hist(tab.reshape(final_shape + (slots,)), e)
+        ctx, st, plan, axes_mask, off_ptr, idx_ptr, keep = cp
+        ebuf = DeviceBuffer(ctx, e.nbytes)
+        ctx.h2d(ebuf.ptr, e, st)
+        tbuf = DeviceBuffer(ctx, nbytes)
+        engine.hist_reset(ctx, tbuf.ptr, n_final, n_bins, st)
+        uniform = (e[0], n_bins / (e[-1] - e[0])) if h["uniform"] else None
+        keep += [ebuf, tbuf]
+        engine.hist_axes(ctx, plan.batch, plan.mask_up.struct, ebuf.ptr, n_bins, uniform, axes_mask, off_ptr, idx_ptr,
+                         tbuf.ptr, st)
+        ctx.d2h(tab, tbuf.ptr, st)
+        ctx.synchronize(st)
+        del keep
+        return self._format_hist(tab.reshape(final_shape + (slots,)), e)
+
+    def _count_plan(self, indexer, compressor, filters, axes, final_shape):
+        """What a counting query (histogram, quantile) launches over: the
+        query's chunks on the device, their plan and the map from each
+        chunk-local output to its table row.  ``(ctx, stream, plan, axes_mask,
+        out_offsets_ptr, out_index_ptr, keep)``, the two pointers None for a
+        full reduction (one row), ``keep`` the buffers to hold until the stream
+        is synchronised; None when the query selects nothing."""
+        ds = self.ds
+        n_final = int(np.prod(final_shape))
         box = self._box_plan(indexer)
         if box is not None:
             dims, coords, table, pool = box
@@ -1092,7 +1153,7 @@ class Active:
             chunk_list = list(indexer)
             n = len(chunk_list)
         if n == 0 or n_final == 0:
-            return self._format_hist(tab.reshape(final_shape + (slots,)), e)
+            return None
         if box is not None:
             ctx, st, buf, offsets, fused = self._ingest(coords, compressor, filters)
             full = _all_full(table, ds.chunks)
@@ -1107,40 +1168,28 @@ class Active:
         axes_mask = 0
         for a in axes:
             axes_mask |= 1 << a
-        ebuf = DeviceBuffer(ctx, e.nbytes)
-        ctx.h2d(ebuf.ptr, e, st)
-        tbuf = DeviceBuffer(ctx, nbytes)
-        engine.hist_reset(ctx, tbuf.ptr, n_final, n_bins, st)
-        uniform = (e[0], n_bins / (e[-1] - e[0])) if h["uniform"] else None
-        keep = [buf, ebuf, tbuf]
+        keep = [buf]
         if len(axes) == ds.ndim:
-            engine.hist_axes(ctx, plan.batch, plan.mask_up.struct, ebuf.ptr, n_bins, uniform, axes_mask, None, None,
-                             tbuf.ptr, st)
+            return ctx, st, plan, axes_mask, None, None, keep
+        # chunk-local output (C order over the kept selected dims) -> final output
+        if box is not None:
+            idx = np.indices([len(p) for p in dims]).reshape(ds.ndim, n)
+            all_projs = ([dims[d][idx[d][k]] for d in range(ds.ndim)] for k in range(n))
         else:
-            # chunk-local output (C order over the kept selected dims) -> final output
-            if box is not None:
-                idx = np.indices([len(p) for p in dims]).reshape(ds.ndim, n)
-                all_projs = ([dims[d][idx[d][k]] for d in range(ds.ndim)] for k in range(n))
-            else:
-                all_projs = (projs for _, projs in chunk_list)
-            sizes, fidx = [], []
-            for projs in all_projs:
-                pos = [np.asarray(p.out_pos, dtype=np.int64) if i not in axes else np.zeros(1, dtype=np.int64)
-                       for i, p in enumerate(projs)]
-                grids = np.meshgrid(*pos, indexing="ij")
-                fidx.append(np.ravel_multi_index([x.reshape(-1) for x in grids], final_shape))
-                sizes.append(grids[0].size)
-            out_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-            meta = np.concatenate([out_off[:-1]] + fidx).astype(np.int64)
-            mbuf = DeviceBuffer(ctx, meta.nbytes)
-            ctx.h2d(mbuf.ptr, meta, st)
-            keep.append(mbuf)
-            engine.hist_axes(ctx, plan.batch, plan.mask_up.struct, ebuf.ptr, n_bins, uniform, axes_mask, mbuf.ptr,
-                             mbuf.ptr + 8 * n, tbuf.ptr, st)
-        ctx.d2h(tab, tbuf.ptr, st)
-        ctx.synchronize(st)
-        del keep
-        return self._format_hist(tab.reshape(final_shape + (slots,)), e)
+            all_projs = (projs for _, projs in chunk_list)
+        sizes, fidx = [], []
+        for projs in all_projs:
+            pos = [np.asarray(p.out_pos, dtype=np.int64) if i not in axes else np.zeros(1, dtype=np.int64)
+                   for i, p in enumerate(projs)]
+            grids = np.meshgrid(*pos, indexing="ij")
+            fidx.append(np.ravel_multi_index([x.reshape(-1) for x in grids], final_shape))
+            sizes.append(grids[0].size)
+        out_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        meta = np.concatenate([out_off[:-1]] + fidx).astype(np.int64)
+        mbuf = DeviceBuffer(ctx, meta.nbytes)
+        ctx.h2d(mbuf.ptr, meta, st)
+        keep.append(mbuf)
+        return ctx, st, plan, axes_mask, mbuf.ptr, mbuf.ptr + 8 * n, keep
 
     def _format_hist(self, tab, e):
         """The int64 counts of a histogram query from its table rows (counts,
@@ -1153,6 +1202,97 @@ class Active:
                     "above": np.ascontiguousarray(tab[..., n_bins + 1]),
                     "nan": np.ascontiguousarray(tab[..., n_bins + 2])}
         return counts
+
+    # -- quantile -------------------------------------------------------------------
+    def _reduce_select(self, indexer, compressor, filters, axes):
+        """quantile: a radix select per output over the keys of its unmasked
+        elements (quantile.keys), most significant digit first.  Every pass
+        counts one digit into table rows of ``2^bits + 3`` slots
+        (pyas_select_axes: the histogram's launch with the digit rule) and a
+        small kernel extends each row's prefix by the digit that holds its
+        rank (pyas_select_step).  The first pass is shared by the query; its
+        per-row ``n`` and ``nan`` come back (pyas_select_totals) and set the
+        ranks (quantile.ranks).  Each distinct vector of ranks is a chain that
+        runs the remaining passes with its own prefixes; the final prefixes
+        (the keys of the order statistics) are all that is copied back.  No
+        table travels to the host."""
+        ds = self.ds
+        qs, method = self._quant["q"], self._quant["method"]
+        qf = qs.reshape(-1)
+        final_shape = tuple(1 if i in axes else n for i, n in enumerate(indexer.shape))
+        n_final = int(np.prod(final_shape))
+        bits = quantile.fit_bits(max(n_final, 1), histogram.TABLE_CAP_BYTES)
+        width = quantile.key_width(ds.dtype)
+        passes = quantile.digits(width, bits)
+        tot = np.zeros((n_final, 2), dtype=np.int64)
+        self._select_stats = {"bits": bits, "passes": 0, "chains": 0}
+        cp = self._count_plan(indexer, compressor, filters, axes, final_shape)
+        if cp is None:
+            return self._format_select(tot, None, final_shape)
+        ctx, st, plan, axes_mask, off_ptr, idx_ptr, keep = cp
+        tbuf = DeviceBuffer(ctx, n_final * ((1 << bits) + 3) * 8)
+        totbuf = DeviceBuffer(ctx, tot.nbytes)
+        keep += [tbuf, totbuf]
+        launched = 0
+
+        def count(prefix_ptr, shift, b):
+            nonlocal launched
+            engine.hist_reset(ctx, tbuf.ptr, n_final, 1 << b, st)
+            engine.select_axes(ctx, plan.batch, plan.mask_up.struct, prefix_ptr, shift, b, axes_mask, off_ptr, idx_ptr,
+                               tbuf.ptr, st)
+            launched += 1
+
+        shift0, b0 = passes[0]
+        count(None, shift0, b0)
+        engine.select_totals(ctx, tbuf.ptr, n_final, b0, totbuf.ptr, st)
+        ctx.d2h(tot, totbuf.ptr, st)
+        ctx.synchronize(st)
+        # ranks among each row's non-NaN elements (a row with a NaN gives NaN whatever its ranks select)
+        h, r_lo, r_hi = quantile.ranks((tot[:, 0] - tot[:, 1])[:, None], qf[None, :], method)
+        chains = {}                      # rank vector -> its position among the chains
+        col_lo, col_hi = [], []
+        for j in range(qf.size):
+            for cols, r in ((col_lo, r_lo), (col_hi, r_hi)):
+                cols.append(chains.setdefault(np.ascontiguousarray(r[:, j]).tobytes(), len(chains)))
+        n_ch = len(chains)
+        ranks = np.stack([np.frombuffer(k, dtype=np.int64) for k in chains]) if n_ch else np.zeros((0, n_final), np.int64)
+        work = np.concatenate([ranks.reshape(-1), np.zeros(n_ch * n_final, dtype=np.int64)])
+        wbuf = DeviceBuffer(ctx, max(work.nbytes, 16))   # every chain's ranks, then every chain's prefixes (zero)
+        keep.append(wbuf)
+        ctx.h2d(wbuf.ptr, work, st)
+        rank_ptr = [wbuf.ptr + 8 * n_final * c for c in range(n_ch)]
+        pre_ptr = [wbuf.ptr + 8 * n_final * (n_ch + c) for c in range(n_ch)]
+        for c in range(n_ch):            # every chain takes its first digit from the shared table
+            engine.select_step(ctx, tbuf.ptr, n_final, b0, rank_ptr[c], pre_ptr[c], None, st)
+        for c in range(n_ch):
+            for shift, b in passes[1:]:
+                count(pre_ptr[c], shift, b)
+                engine.select_step(ctx, tbuf.ptr, n_final, b, rank_ptr[c], pre_ptr[c], None, st)
+        out = np.zeros((n_ch, n_final), dtype=np.uint64)
+        if n_ch:
+            ctx.d2h(out, pre_ptr[0], st)
+        ctx.synchronize(st)
+        del keep
+        self._select_stats = {"bits": bits, "passes": launched, "chains": n_ch}
+        vals = quantile.values(out, ds.dtype).astype(np.float64)
+        return self._format_select(tot, quantile.finalize(vals[col_lo].T, vals[col_hi].T, h, method), final_shape)
+
+    def _format_select(self, tot, res, final_shape):
+        """The float64 masked result of a quantile query (rows x q) from its
+        per-row ``(n, nan)`` and interpolated values, or its components."""
+        qs = self._quant["q"]
+        n, nan = tot[:, 0], tot[:, 1]
+        if res is None:
+            res = np.zeros((tot.shape[0], qs.size), dtype=np.float64)
+        res = np.where((nan > 0)[:, None], np.nan, res)
+        res = np.where((n == 0)[:, None], 0.0, res)
+        shape = final_shape + qs.shape
+        out = np.ma.MaskedArray(np.ascontiguousarray(res.reshape(shape)),
+                                mask=np.ascontiguousarray(np.broadcast_to((n == 0)[:, None], res.shape).reshape(shape)))
+        if self._components:
+            return {"quantile": out, "n": np.ascontiguousarray(n.reshape(final_shape)),
+                    "nan": np.ascontiguousarray(nan.reshape(final_shape))}
+        return out
 
     # -- weighted mean / sum ------------------------------------------------------
     def _weight_tables(self, coords):

@@ -1668,6 +1668,50 @@ int pyas_wsum_combine_grid(pyas_ctx *ctx, const pyas_wsum *in, const pyas_grid *
     return PYAS_OK;
 }
 
+// The launch shapes shared by the counting kernels (binned counts and the
+// radix select's digit counts).
+// k_hist_full / k_qsel_full: log2 of the copies of an LDS table of `slots` slots (and a spare one)
+static int hist_lds_copies(int64_t slots) {
+    int shift = 5;   // kHistMaxCopies
+    while ((1 << shift) > pyas::kHistMinCopies && (slots + 1) * 4 * (1 << shift) > pyas::kHistTabBytes) --shift;
+    return shift;
+}
+
+// k_hist_full / k_qsel_full: the grid over `pairs` (chunk, tile) pairs
+// (PYAS_HIST_WGS: the grid's cap, read per call: tests and benches switch it;
+// default 4 per CU)
+static int64_t hist_full_grid(const pyas_ctx *ctx, int64_t pairs) {
+    const char *e = getenv("PYAS_HIST_WGS");
+    int64_t grid = e && *e ? atoll(e) : 4 * (int64_t)ctx->n_cu;
+    if (grid < 1) grid = 1;
+    if (grid > 65536) grid = 65536;
+    if (grid > pairs) grid = pairs;
+    return grid;
+}
+
+// k_hist_axes / k_qsel_axes: workgroups per chunk, and the waves per output (`split`) when the innermost dim is reduced
+static int64_t hist_axes_shape(int64_t chunk_elems, int64_t keep_elems, bool row, int32_t &split_out) {
+    int64_t bpc;
+    split_out = 1;
+    if (row) {
+        // a wave per 1,024 reduced positions of an output, so a chunk with few
+        // outputs still fills its workgroups
+        constexpr int64_t kWaves = pyas::kBlock / pyas::kWave;
+        const int64_t red_elems = chunk_elems / keep_elems;
+        int64_t split = (red_elems + 1023) / 1024;
+        if (split * keep_elems > 64 * kWaves) split = (64 * kWaves) / keep_elems;
+        if (split < 1) split = 1;
+        split_out = (int32_t)split;
+        bpc = (keep_elems * split + kWaves * 16 - 1) / (kWaves * 16);
+        if (split > 1) bpc = (keep_elems * split + kWaves - 1) / kWaves;
+    } else {
+        bpc = (keep_elems + pyas::kBlock - 1) / pyas::kBlock;
+    }
+    if (bpc > 64) bpc = 64;
+    if (bpc < 1) bpc = 1;
+    return bpc;
+}
+
 int pyas_hist_axes(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask, const pyas_hist *hist,
                    uint32_t axes_mask, const int64_t *out_offsets, const int64_t *out_index, int64_t *table,
                    void *stream) {
@@ -1706,19 +1750,13 @@ int pyas_hist_axes(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask
     if (full && hist->n_bins <= pyas::kHistLdsBins) {
         // counts in LDS: a few workgroups per CU, each over a contiguous range
         // of (chunk, tile) pairs, so a bin's global word takes one add per
-        // workgroup (PYAS_HIST_WGS: the grid's cap, read per call: tests and
-        // benches switch it; default 4 per CU)
+        // workgroup
         const int64_t tpc = tiles_per_chunk(ctx, x.r.chunk_elems * es);
         const int64_t pairs = n * tpc;
         if (pairs >= (int64_t(1) << 31)) return fail(PYAS_ENOTSUP, "grid of %lld tiles", (long long)pairs);
         const int64_t slots = (int64_t)hist->n_bins + 3;
-        int shift = 5;   // kHistMaxCopies
-        while ((1 << shift) > pyas::kHistMinCopies && (slots + 1) * 4 * (1 << shift) > pyas::kHistTabBytes) --shift;
-        const char *e = getenv("PYAS_HIST_WGS");
-        int64_t grid = e && *e ? atoll(e) : 4 * (int64_t)ctx->n_cu;
-        if (grid < 1) grid = 1;
-        if (grid > 65536) grid = 65536;
-        if (grid > pairs) grid = pairs;
+        const int shift = hist_lds_copies(slots);
+        const int64_t grid = hist_full_grid(ctx, pairs);
         x.bpc = tpc;
         x.n_pairs = pairs;
         x.shift = shift;
@@ -1731,26 +1769,8 @@ int pyas_hist_axes(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask
     for (int d = 0; d < batch->ndim; ++d)
         if (!((axes_mask >> d) & 1u)) keep_elems *= batch->chunk_shape[d];
     x.row = ((axes_mask >> (batch->ndim - 1)) & 1u) != 0;
-    int64_t bpc;
-    x.split = 1;
-    if (x.row) {
-        // a wave per 1,024 reduced positions of an output, so a chunk with few
-        // outputs still fills its workgroups
-        constexpr int64_t kWaves = pyas::kBlock / pyas::kWave;
-        const int64_t red_elems = x.r.chunk_elems / keep_elems;
-        int64_t split = (red_elems + 1023) / 1024;
-        if (split * keep_elems > 64 * kWaves) split = (64 * kWaves) / keep_elems;
-        if (split < 1) split = 1;
-        x.split = (int32_t)split;
-        bpc = (keep_elems * split + kWaves * 16 - 1) / (kWaves * 16);
-        if (split > 1) bpc = (keep_elems * split + kWaves - 1) / kWaves;
-    } else {
-        bpc = (keep_elems + pyas::kBlock - 1) / pyas::kBlock;
-    }
-    if (bpc > 64) bpc = 64;
-    if (bpc < 1) bpc = 1;
-    x.bpc = bpc;
-    const int64_t grid = n * bpc;
+    x.bpc = hist_axes_shape(x.r.chunk_elems, keep_elems, x.row, x.split);
+    const int64_t grid = n * x.bpc;
     if (grid >= (int64_t(1) << 31)) return fail(PYAS_ENOTSUP, "grid too large");
     PYAS_HIP(pyas::launch_hist_axes(batch->dtype, x, shuf, grid, st));
     return PYAS_OK;
@@ -1763,6 +1783,96 @@ int pyas_hist_reset(pyas_ctx *ctx, int64_t *table, int64_t n_rows, int32_t n_bin
     if (!table) return fail(PYAS_EINVAL, "table is NULL");
     PYAS_HIP(hipSetDevice(ctx->device));
     PYAS_HIP(hipMemsetAsync(table, 0, (size_t)n_rows * (size_t)(n_bins + 3) * sizeof(int64_t), (hipStream_t)stream));
+    return PYAS_OK;
+}
+
+int pyas_select_axes(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask, const pyas_select *sel,
+                     uint32_t axes_mask, const int64_t *out_offsets, const int64_t *out_index, int64_t *table,
+                     void *stream) {
+    if (!ctx) return fail(PYAS_EINVAL, "ctx is NULL");
+    if (batch && (batch->ndim < 1 || batch->ndim > PYAS_MAX_DIMS))
+        return fail(PYAS_ENOTSUP, "chunk rank %d outside 1..%d", batch->ndim, PYAS_MAX_DIMS);
+    pyas::QselArgs x;
+    std::memset(&x, 0, sizeof(x));
+    int es;
+    bool shuf, bsw, masked;
+    int rc = prepare(ctx, batch, mask, x.r, es, shuf, bsw, masked);
+    if (rc) return rc;
+    if (axes_mask >> batch->ndim) return fail(PYAS_EINVAL, "axes mask 0x%x beyond rank %d", axes_mask, batch->ndim);
+    if (!sel) return fail(PYAS_EINVAL, "select is NULL");
+    const int width = es == 8 ? 64 : 32;
+    if (sel->bits < 1 || sel->bits > PYAS_SELECT_MAX_BITS)
+        return fail(PYAS_EINVAL, "bits = %d outside 1..%d", sel->bits, PYAS_SELECT_MAX_BITS);
+    if (sel->shift < 0 || sel->shift + sel->bits > width)
+        return fail(PYAS_EINVAL, "digit of %d bits at %d lies outside the %d-bit key", sel->bits, sel->shift, width);
+    if (!sel->prefix && sel->shift + sel->bits != width)
+        return fail(PYAS_EINVAL, "prefix is NULL below the key's first digit");
+    const int64_t n = batch->n_chunks;
+    if (n == 0) return PYAS_OK;
+    if (!table) return fail(PYAS_EINVAL, "table is NULL");
+    const bool full = axes_mask == (1u << batch->ndim) - 1u;
+    if (!full && !out_offsets) return fail(PYAS_EINVAL, "out_offsets is NULL");
+    PYAS_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    x.axes = axes_mask;
+    x.out_offsets = out_offsets;
+    x.out_index = out_index;
+    x.table = (unsigned long long *)table;
+    x.prefix = (const unsigned long long *)sel->prefix;
+    x.shift = sel->shift;
+    x.bits = sel->bits;
+    x.bswap = bsw;
+    x.masked = masked;
+    if (full) {
+        // counts in LDS, the launch shape of pyas_hist_axes' full form
+        const int64_t tpc = tiles_per_chunk(ctx, x.r.chunk_elems * es);
+        const int64_t pairs = n * tpc;
+        if (pairs >= (int64_t(1) << 31)) return fail(PYAS_ENOTSUP, "grid of %lld tiles", (long long)pairs);
+        const int64_t slots = ((int64_t)1 << sel->bits) + 3;
+        x.shift_copies = hist_lds_copies(slots);
+        x.bpc = tpc;
+        x.n_pairs = pairs;
+        const size_t lds = (size_t)((slots + 1) << x.shift_copies) * sizeof(uint32_t);
+        PYAS_HIP(pyas::launch_qsel_full(batch->dtype, x, shuf, hist_full_grid(ctx, pairs), lds, st));
+        return PYAS_OK;
+    }
+    int64_t keep_elems = 1;
+    for (int d = 0; d < batch->ndim; ++d)
+        if (!((axes_mask >> d) & 1u)) keep_elems *= batch->chunk_shape[d];
+    x.row = ((axes_mask >> (batch->ndim - 1)) & 1u) != 0;
+    x.bpc = hist_axes_shape(x.r.chunk_elems, keep_elems, x.row, x.split);
+    const int64_t grid = n * x.bpc;
+    if (grid >= (int64_t(1) << 31)) return fail(PYAS_ENOTSUP, "grid too large");
+    PYAS_HIP(pyas::launch_qsel_axes(batch->dtype, x, shuf, grid, st));
+    return PYAS_OK;
+}
+
+int pyas_select_step(pyas_ctx *ctx, const int64_t *table, int64_t n_rows, int32_t bits, const int64_t *rank,
+                     uint64_t *prefix, const int64_t *below_base, void *stream) {
+    if (!ctx) return fail(PYAS_EINVAL, "ctx is NULL");
+    if (n_rows < 0) return fail(PYAS_EINVAL, "n_rows = %lld", (long long)n_rows);
+    if (bits < 1 || bits > PYAS_SELECT_MAX_BITS)
+        return fail(PYAS_EINVAL, "bits = %d outside 1..%d", bits, PYAS_SELECT_MAX_BITS);
+    if (n_rows == 0) return PYAS_OK;
+    if (!table || !rank || !prefix) return fail(PYAS_EINVAL, "NULL argument");
+    if ((n_rows + 3) / 4 >= (int64_t(1) << 31)) return fail(PYAS_ENOTSUP, "grid too large");
+    PYAS_HIP(hipSetDevice(ctx->device));
+    PYAS_HIP(pyas::launch_qsel_step((const unsigned long long *)table, n_rows, bits, rank,
+                                    (unsigned long long *)prefix, below_base, (hipStream_t)stream));
+    return PYAS_OK;
+}
+
+int pyas_select_totals(pyas_ctx *ctx, const int64_t *table, int64_t n_rows, int32_t bits, int64_t *totals,
+                       void *stream) {
+    if (!ctx) return fail(PYAS_EINVAL, "ctx is NULL");
+    if (n_rows < 0) return fail(PYAS_EINVAL, "n_rows = %lld", (long long)n_rows);
+    if (bits < 1 || bits > PYAS_SELECT_MAX_BITS)
+        return fail(PYAS_EINVAL, "bits = %d outside 1..%d", bits, PYAS_SELECT_MAX_BITS);
+    if (n_rows == 0) return PYAS_OK;
+    if (!table || !totals) return fail(PYAS_EINVAL, "NULL argument");
+    if ((n_rows + 3) / 4 >= (int64_t(1) << 31)) return fail(PYAS_ENOTSUP, "grid too large");
+    PYAS_HIP(hipSetDevice(ctx->device));
+    PYAS_HIP(pyas::launch_qsel_totals((const unsigned long long *)table, n_rows, bits, totals, (hipStream_t)stream));
     return PYAS_OK;
 }
 

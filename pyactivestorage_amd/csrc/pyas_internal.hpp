@@ -318,6 +318,29 @@ struct HistArgs {
 };
 hipError_t launch_hist_full(int dtype, const HistArgs &a, bool shuf, int64_t grid, size_t lds, hipStream_t st);
 hipError_t launch_hist_axes(int dtype, const HistArgs &a, bool shuf, int64_t grid, hipStream_t st);
+// radix select (pyas_select.hip): one digit's counts per pass, in the histogram's table rows (2^bits + 3 slots)
+constexpr int kQselMaxBits = 11;      // 2^11 slots: the most of k_hist_full's LDS tables (kHistLdsBins)
+struct QselArgs {
+    ReduceArgs r;                     // r.out unused
+    uint32_t axes;                    // reduced dims
+    int64_t bpc;                      // k_qsel_axes: workgroups per chunk; k_qsel_full: tiles per chunk
+    int64_t n_pairs;                  // k_qsel_full: n_chunks * bpc (chunk, tile) pairs, shared out over the grid
+    const int64_t *out_offsets;       // NULL (every dim reduced): row 0
+    const int64_t *out_index;         // NULL: the identity
+    unsigned long long *table;
+    const unsigned long long *prefix; // pyas_select: one per table row, NULL on the first pass
+    int32_t shift, bits;
+    int32_t shift_copies;             // k_qsel_full: log2 of the LDS table's copies
+    int32_t split;                    // k_qsel_axes, innermost dim reduced: waves per output
+    bool bswap, masked;
+    bool row;                         // innermost dim reduced
+};
+hipError_t launch_qsel_full(int dtype, const QselArgs &a, bool shuf, int64_t grid, size_t lds, hipStream_t st);
+hipError_t launch_qsel_axes(int dtype, const QselArgs &a, bool shuf, int64_t grid, hipStream_t st);
+hipError_t launch_qsel_step(const unsigned long long *table, int64_t n_rows, int32_t bits, const int64_t *rank,
+                            unsigned long long *prefix, const int64_t *below_base, hipStream_t st);
+hipError_t launch_qsel_totals(const unsigned long long *table, int64_t n_rows, int32_t bits, int64_t *totals,
+                              hipStream_t st);
 // host ingest (pyas_ingest.hip): pread ring -> pinned slots -> H2D
 struct Ingest;
 Ingest *ingest_create(int device);

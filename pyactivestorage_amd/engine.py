@@ -259,6 +259,33 @@ def hist_reset(ctx: Context, table_ptr, n_rows: int, n_bins: int, stream) -> Non
     _lib.check(ctx.lib.pyas_hist_reset(ctx.handle, table_ptr, int(n_rows), int(n_bins), stream), "pyas_hist_reset")
 
 
+def select_axes(ctx: Context, batch: _lib.Batch, mask: _lib.Mask, prefix_ptr, shift: int, bits: int, axes_mask: int,
+                out_offsets_ptr, out_index_ptr, table_ptr, stream) -> None:
+    """pyas_select_axes: one pass of the radix select, the counts of the digit
+    of ``bits`` bits at ``shift`` added into int64 table rows of
+    ``2^bits + 3`` slots (digit counts, below, above, nan).  ``prefix_ptr``:
+    the device uint64 prefixes, one per row (None on the first pass); the
+    other arguments as for :func:`hist_axes`."""
+    s = _lib.Select(prefix_ptr, int(shift), int(bits))
+    _lib.check(ctx.lib.pyas_select_axes(ctx.handle, ctypes.byref(batch), ctypes.byref(mask), ctypes.byref(s),
+                                        int(axes_mask), out_offsets_ptr, out_index_ptr, table_ptr, stream),
+               "pyas_select_axes")
+
+
+def select_step(ctx: Context, table_ptr, n_rows: int, bits: int, rank_ptr, prefix_ptr, below_base_ptr,
+                stream) -> None:
+    """pyas_select_step: extend every row's prefix by the digit that holds
+    its rank (all pointers device; ``below_base_ptr`` may be None)."""
+    _lib.check(ctx.lib.pyas_select_step(ctx.handle, table_ptr, int(n_rows), int(bits), rank_ptr, prefix_ptr,
+                                        below_base_ptr, stream), "pyas_select_step")
+
+
+def select_totals(ctx: Context, table_ptr, n_rows: int, bits: int, totals_ptr, stream) -> None:
+    """pyas_select_totals: ``(n, nan)`` int64 per table row, on the device."""
+    _lib.check(ctx.lib.pyas_select_totals(ctx.handle, table_ptr, int(n_rows), int(bits), totals_ptr, stream),
+               "pyas_select_totals")
+
+
 def wsum_axes(ctx: Context, batch: _lib.Batch, mask: _lib.Mask, pool_ptr, origin_ptr, axes_mask: int,
               out_offsets_ptr, out_ptr, stream) -> None:
     """pyas_wsum_axes: count / sum w / sum w x records per chunk output, laid

@@ -118,7 +118,9 @@ def quantile(counts, bin_edges, q):
     bin.  The ``ceil(k)``-th smallest value lies in the same bin, so the result
     is within one bin width of it.  ``counts``: ``(..., n_bins)``; ``q``: a
     scalar or 1-D in [0, 1].  Returns float64 of shape ``counts.shape[:-1] +
-    q.shape``; NaN where nothing was counted."""
+    q.shape``; NaN where nothing was counted.  For the exact order
+    statistics of a variable use ``Active.quantile`` / ``Active.median`` (a
+    radix select on the device, equal to ``np.quantile``)."""
     c = np.asarray(counts, dtype=np.int64)
     e = np.asarray(bin_edges, dtype=np.float64)
     qs = np.asarray(q, dtype=np.float64)
