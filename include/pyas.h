@@ -554,6 +554,47 @@ int pyas_moments_combine_segments(pyas_ctx *ctx, const pyas_moments *in, const i
 int pyas_moments_combine_grid(pyas_ctx *ctx, const pyas_moments *in, const pyas_grid *grid,
                               pyas_moments *out, void *stream);
 
+/* ---- co-moments of two variables (Active.cov / Active.corr) -------------------
+ * Partial record of a masked covariance over a set of pairs (48 bytes):
+ * count pairs unmasked on both sides; mean_x, mean_y of them;
+ * m2_x = sum (x - mean_x)^2, m2_y = sum (y - mean_y)^2 and
+ * cxy = sum (x - mean_x)(y - mean_y)  (all in f64).  count == 0 is neutral
+ * (the other fields ignored; written as 0).  Values convert to f64 as
+ * astype(float64) does.  One pass: each lane keeps shifts Kx, Ky (its first
+ * counted pair) with sum (x-Kx), sum (y-Ky), sum (x-Kx)^2, sum (y-Ky)^2 and
+ * sum (x-Kx)(y-Ky) in f64 (FMA); lanes, waves, tiles and chunks merge in the
+ * fixed order of the moments records with
+ *   d_x = mean_x_b - mean_x_a;  d_y = mean_y_b - mean_y_a;
+ *   cxy = cxy_a + cxy_b + d_x d_y n_a n_b/n
+ * and the means and m2s exactly as pyas_moments merges them, in the same
+ * operation order (a side with count 0 is skipped, not multiplied through), so
+ * results are bit-identical from run to run.  The m2s are clamped at 0, cxy is
+ * not.  An unmasked NaN or +-inf on either side of a counted pair gives a NaN
+ * cxy (and a NaN m2 on that side). */
+typedef struct { int64_t count; double mean_x, mean_y, m2_x, m2_y, cxy; } pyas_comoments;
+
+/* pyas_moments_axes over two variables: chunk c of y pairs with chunk c of x.
+ * x and y must agree in ndim, chunk_shape and n_chunks (PYAS_EINVAL) and in
+ * dtype (PYAS_ENOTSUP).  sel and index_pool are read from x only: y's are
+ * ignored, the selection of both sides is x's.  data, offsets, shuffle,
+ * byteswap and the mask are per side; a pair counts when neither mask_x masks
+ * its x nor mask_y its y, and the mask tables of each side are indexed by the
+ * same selection position.  Outputs, out_offsets and the other errors as
+ * pyas_moments_axes; PYAS_EINVAL when a batch is NULL.  With every dim in
+ * axes_mask a selection that is one contiguous run streams both buffers with
+ * 16-byte loads when both chunk bases are misaligned alike (base & 15), and is
+ * walked per element otherwise. */
+int pyas_comoments_axes(pyas_ctx *ctx, const pyas_batch *x, const pyas_mask *mask_x,
+                        const pyas_batch *y, const pyas_mask *mask_y, uint32_t axes_mask,
+                        const int64_t *out_offsets, pyas_comoments *out, void *stream);
+/* pyas_moments_combine_segments / pyas_moments_combine_grid for comoments
+ * records (same orders, same errors). */
+int pyas_comoments_combine_segments(pyas_ctx *ctx, const pyas_comoments *in, const int64_t *index,
+                                    const int64_t *seg_offsets, int64_t n_segments,
+                                    pyas_comoments *out, void *stream);
+int pyas_comoments_combine_grid(pyas_ctx *ctx, const pyas_comoments *in, const pyas_grid *grid,
+                                pyas_comoments *out, void *stream);
+
 /* ---- weighted sums (Active.mean / Active.sum with weights=) -----------------
  * Partial record of a weighted mean over a set of elements (32 bytes):
  * count unmasked elements; sw = sum w; swx = sum w x  (f64).  The all-zero

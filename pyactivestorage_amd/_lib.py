@@ -43,6 +43,12 @@ class Moments(ctypes.Structure):
                 ("reserved", ctypes.c_uint64)]
 
 
+class Comoments(ctypes.Structure):
+    """pyas_comoments: count, means, m2s and cxy = sum (x - mean_x)(y - mean_y) of a set of pairs."""
+    _fields_ = [("count", ctypes.c_int64), ("mean_x", ctypes.c_double), ("mean_y", ctypes.c_double),
+                ("m2_x", ctypes.c_double), ("m2_y", ctypes.c_double), ("cxy", ctypes.c_double)]
+
+
 class Wsum(ctypes.Structure):
     """pyas_wsum: count, sum w and sum w x of a set of elements."""
     _fields_ = [("count", ctypes.c_int64), ("sw", ctypes.c_double), ("swx", ctypes.c_double),
@@ -180,6 +186,8 @@ PARTIAL_NBYTES = ctypes.sizeof(Partial)
 assert PARTIAL_NBYTES == 32
 MOMENTS_NBYTES = ctypes.sizeof(Moments)
 assert MOMENTS_NBYTES == 32
+COMOMENTS_NBYTES = ctypes.sizeof(Comoments)
+assert COMOMENTS_NBYTES == 48
 WSUM_NBYTES = ctypes.sizeof(Wsum)
 assert WSUM_NBYTES == 32
 
@@ -238,6 +246,10 @@ SIGNATURES = {
     "pyas_moments_axes": [_vp, ctypes.POINTER(Batch), ctypes.POINTER(Mask), _u32, _vp, _vp, _vp],
     "pyas_moments_combine_segments": [_vp, _vp, _vp, _vp, _i64, _vp, _vp],
     "pyas_moments_combine_grid": [_vp, _vp, ctypes.POINTER(Grid), _vp, _vp],
+    "pyas_comoments_axes": [_vp, ctypes.POINTER(Batch), ctypes.POINTER(Mask), ctypes.POINTER(Batch),
+                            ctypes.POINTER(Mask), _u32, _vp, _vp, _vp],
+    "pyas_comoments_combine_segments": [_vp, _vp, _vp, _vp, _i64, _vp, _vp],
+    "pyas_comoments_combine_grid": [_vp, _vp, ctypes.POINTER(Grid), _vp, _vp],
     "pyas_wsum_axes": [_vp, ctypes.POINTER(Batch), ctypes.POINTER(Mask), ctypes.POINTER(Weights), _u32, _vp, _vp,
                        _vp],
     "pyas_wsum_combine_segments": [_vp, _vp, _vp, _vp, _i64, _vp, _vp],

@@ -35,7 +35,10 @@ added by every chunk straight into the result table (``pyas_hist_axes``,
 ``_reduce_hist``); and ``.quantile(q, axis, method)`` / ``.median(axis)``,
 exact order statistics by a radix select over keys, a few passes of digit
 counts in the histogram's table (``pyas_select_axes``, ``pyas_select_step``,
-``_reduce_select``).
+``_reduce_select``); and ``.cov(other, axis, ddof)`` / ``.corr(other, axis)``
+over a second ``Active``, one pass of count / means / m2s / cxy records over
+both variables' chunks (``pyas_comoments_axes``) merged like the var records
+(``_reduce_comoments``).
 """
 from __future__ import annotations
 
@@ -47,7 +50,7 @@ import warnings
 
 import numpy as np
 
-from . import _lib, engine, histogram, moments, quantile, selection, weighted, zerosign
+from . import _lib, comoments, engine, histogram, moments, quantile, selection, weighted, zerosign
 from .batch import ReductionPlan, _all_full
 from .device import DeviceBuffer, get_context
 from .dtypes import native, sum_dtype
@@ -61,6 +64,7 @@ from .variable import ChunkedVariable, decode_filters, get_missing_attributes
 _ALIGN = 256
 _MOMENTS_SEG = 64   # records a thread folds per level of a full var / std reduction
 _WSUM_SEG = 64      # the same for a full weighted mean / sum reduction
+_COMOMENTS_SEG = 64  # and for a full cov / corr reduction
 _RESIDENT_LOCK = threading.Lock()
 _RESIDENT_CV = threading.Condition(_RESIDENT_LOCK)   # slot state changes
 _EMPTY, _LOADING, _LOADED = 0, 1, 2
@@ -331,6 +335,7 @@ class Active:
         self._weights = None            # mean / sum: {dim: float64 vector} of the next query
         self._hist = None               # histogram: the bins of the next query (_check_hist)
         self._quant = None              # quantile: {"q": float64 (0-D or 1-D), "method": str} of the next query
+        self._co = None                 # cov / corr: the second variable's Active of the next query
         self._select_stats = None       # the last quantile query: its digit width, count launches and chains
         self._max_threads = int(max_threads)
         self.device = device
@@ -374,6 +379,7 @@ class Active:
         self._weights = None
         self._hist = None
         self._quant = None
+        self._co = None
 
     @property
     def weights(self):
@@ -460,6 +466,30 @@ class Active:
         """Standard deviation: the square root of :meth:`var`."""
         return self._set_moments("std", axis, ddof)
 
+    def cov(self, other, axis=None, ddof=0):
+        """Covariance with ``other``, an ``Active`` over a second variable of
+        the same shape, chunks and dtype (byte order and filters may differ;
+        it may be this object): ``cxy / (n - ddof)`` in float64 over the pairs
+        selected and unmasked in both variables, each side under its own
+        missing-data attributes; ``np.cov(xs, ys, ddof=ddof)[0, 1]`` of the
+        compressed float64 pairs.  Masked where ``n - ddof <= 0``; NaN where a
+        counted pair holds a NaN or an infinity.  One pass on the device over
+        both variables' chunks (pyas_comoments_axes).  With ``components`` the
+        result is a dict of ``n``, ``mean_x``, ``mean_y``,
+        ``m2_x = sum (x - mean_x)^2``, ``m2_y`` and
+        ``cxy = sum (x - mean_x)(y - mean_y)``: the slope of the regression of
+        ``other`` on this variable is ``cxy / m2_x``, and
+        ``comoments.merge`` combines the components of disjoint selections.
+        The settings hold for one query."""
+        return self._set_comoments("cov", other, axis, ddof)
+
+    def corr(self, other, axis=None):
+        """Pearson's correlation with ``other`` (see :meth:`cov`):
+        ``cxy / sqrt(m2_x) / sqrt(m2_y)`` clipped to [-1, 1] as
+        ``np.corrcoef`` clips.  Masked where no pair is counted; NaN, not
+        masked, where either variable is constant over the counted pairs."""
+        return self._set_comoments("corr", other, axis, 0)
+
     def histogram(self, bins=10, range=None, axis=None):   # noqa: A002 - NumPy's argument name
         """Binned counts of the unmasked elements, one pass on the device
         (pyas_hist_axes).  Each element converts to float64 as
@@ -524,6 +554,23 @@ class Active:
             self._axis = axis
         return self
 
+    def _set_comoments(self, method, other, axis, ddof):
+        if not isinstance(other, Active):
+            raise TypeError(f"{method}: other must be an Active over the second variable. Got {other!r}")
+        x, y = self.ds, other.ds
+        if tuple(x.shape) != tuple(y.shape) or tuple(x.chunks) != tuple(y.chunks):
+            raise ValueError(f"{method}: the two variables must agree in shape and chunk shape. Got shape "
+                             f"{tuple(x.shape)} in chunks {tuple(x.chunks)} and shape {tuple(y.shape)} in chunks "
+                             f"{tuple(y.chunks)}")
+        if x.dtype.kind != y.dtype.kind or x.dtype.itemsize != y.dtype.itemsize:
+            raise NotImplementedError(f"{method}: the two variables must have the same dtype up to byte order. "
+                                      f"Got {x.dtype.str} and {y.dtype.str}")
+        if other.device != self.device:
+            raise ValueError(f"{method}: the two Active objects are on devices {self.device} and {other.device}")
+        self._set_moments(method, axis, ddof)
+        self._co = other
+        return self
+
     # -- query -------------------------------------------------------------
     def __getitem__(self, index):
         self.missing = get_missing_attributes(self.ds.attrs)
@@ -536,6 +583,7 @@ class Active:
             self._weights = None         # weights are per query
             self._hist = None            # and so are a histogram's bins
             self._quant = None           # and a quantile's q and method
+            self._co = None              # and a cov / corr's second variable
             for store in held:
                 _unhold(store)
             self._held.stores = []
@@ -556,15 +604,18 @@ class Active:
         quant = self._method == "quantile"
         if quant and self.group is not None:
             raise NotImplementedError("quantile with group=…: order statistics are selected on one GPU only")
+        co = self._method in ("cov", "corr")
+        if co and (self.group is not None or self._co.group is not None):
+            raise NotImplementedError("cov/corr with group=…: co-moments are reduced on one GPU only")
         if self._axis is None:
             self._axis = tuple(range(ds.ndim))
         elif isinstance(self._axis, int):
             self._axis = (self._axis,)
         cache_key = None
-        # (var / std, weighted, histogram and quantile queries bypass the plan cache: its plans replay pyas_partial
-        # launches)
+        # (var / std, weighted, histogram, quantile and cov / corr queries bypass the plan cache: its plans replay
+        # pyas_partial launches)
         if self.resident and self.group is None and self._method is not None and not second and not has_w \
-                and not hist and not quant:
+                and not hist and not quant and not co:
             ikey = _index_key(index)
             if ikey is not None:
                 cache_key = (ikey, self._norm_axes(), _missing_key(self.missing))
@@ -590,6 +641,8 @@ class Active:
             return self._reduce_select(indexer, compressor, filters, self._norm_axes())
         if has_w:
             return self._reduce_weighted(indexer, compressor, filters, self._norm_axes())
+        if co:
+            return self._reduce_comoments(indexer, compressor, filters, self._norm_axes())
         return self._reduce(indexer, compressor, filters, self._norm_axes(), cache_key)
 
     def _norm_axes(self):
@@ -1066,6 +1119,145 @@ class Active:
         del keep
         return self._format_moments(final.reshape(final_shape))
 
+    # -- cov / corr -----------------------------------------------------------
+    def _ingest_other(self, other, coords):
+        """``other``'s chunks ``coords`` through its own ingest (its filter
+        pipeline, its resident store); the stores it holds join this query's,
+        so ``__getitem__`` releases both sides together."""
+        yds = other.ds
+        compressor, filters = (None, None) if not yds.filter_pipeline else \
+            decode_filters(yds.filter_pipeline, yds.dtype.itemsize, yds.name)
+        prev = getattr(other._held, "stores", None)
+        other._held.stores = self._held.stores
+        other.data_read = 0
+        try:
+            got = other._ingest(coords, compressor, filters)
+        finally:
+            other._held.stores = prev
+        self.data_read += other.data_read
+        return got
+
+    def _reduce_comoments(self, indexer, compressor, filters, axes):
+        """cov / corr: per-chunk count / means / m2s / cxy records of the two
+        variables' pairs (pyas_comoments_axes: one plan per side, over the same
+        chunk list and selections) merged in the order :meth:`_reduce_moments`
+        merges its records in: a full reduction in chunk order, a box query
+        over the chunk layers of each output (pyas_comoments_combine_grid),
+        anything else over host-built segments
+        (pyas_comoments_combine_segments)."""
+        ds, other = self.ds, self._co
+        yds = other.ds
+        missing_y = get_missing_attributes(yds.attrs)
+        final_shape = tuple(1 if i in axes else n for i, n in enumerate(indexer.shape))
+        n_final = int(np.prod(final_shape))
+        final = np.zeros(n_final, dtype=engine.comoments_dtype)
+        fmt = self._format_comoments
+        # (vector fill/missing values on either side need per-chunk selections)
+        box = None if any(m is not None and np.size(m) != 1 for m in missing_y) else self._box_plan(indexer)
+        dims = None
+        if box is not None:
+            dims, coords, table, pool = box
+            n = len(coords)
+        else:
+            chunk_list = list(indexer)
+            n = len(chunk_list)
+            coords = [c for c, _ in chunk_list]
+        if n == 0 or n_final == 0:
+            return fmt(final.reshape(final_shape))
+        ctx, st, buf, offsets, fused = self._ingest(coords, compressor, filters)
+        if other is self:
+            ybuf, yoffsets, yfused = buf, offsets, fused
+        else:
+            _, yst, ybuf, yoffsets, yfused = self._ingest_other(other, coords)
+            if yst != st:    # (one stream per thread and device: both ingests share it)
+                ctx.stream_wait(st, yst)
+        if box is not None:
+            full = _all_full(table, ds.chunks)
+            sel = dict(sel_table=None if full else table, index_pool=None if full else pool)
+        else:
+            sel = dict(selections=[self._chunk_sel(projs) for _, projs in chunk_list])
+        plan = ReductionPlan(ctx, ds.dtype, ds.chunks, buf.ptr, offsets, shuffle=fused, missing=self.missing,
+                             stream=st, **sel)
+        plan_y = ReductionPlan(ctx, yds.dtype, yds.chunks, ybuf.ptr, yoffsets, shuffle=yfused, missing=missing_y,
+                               stream=st, **sel)
+        axes_mask = 0
+        for a in axes:
+            axes_mask |= 1 << a
+        nb = _lib.COMOMENTS_NBYTES
+        fin = DeviceBuffer(ctx, n_final * nb)
+        keep = [buf, ybuf]
+
+        def reduce_axes(off_ptr, out_ptr):
+            engine.comoments_axes(ctx, plan.batch, plan.mask_up.struct, plan_y.batch, plan_y.mask_up.struct,
+                                  axes_mask, off_ptr, out_ptr, st)
+        if len(axes) == ds.ndim:
+            # one record per chunk, folded in chunk order: groups of
+            # _COMOMENTS_SEG consecutive records per thread, level after level
+            # (one allocation: every level's records, then every level's segment bounds)
+            levels, m = [], n
+            while True:
+                n_seg = -(-m // _COMOMENTS_SEG)
+                levels.append((n_seg, np.minimum(np.arange(n_seg + 1, dtype=np.int64) * _COMOMENTS_SEG, m)))
+                if n_seg == 1:
+                    break
+                m = n_seg
+            segs = np.concatenate([seg for _, seg in levels])
+            n_rec = n + sum(n_seg for n_seg, _ in levels[:-1])
+            work = DeviceBuffer(ctx, n_rec * nb + segs.nbytes)
+            keep.append(work)
+            cur, sptr = work.ptr, work.ptr + n_rec * nb
+            ctx.h2d(sptr, segs, st)
+            reduce_axes(None, cur)
+            nxt = cur + n * nb
+            for n_seg, seg in levels:
+                dst = fin.ptr if n_seg == 1 else nxt
+                engine.comoments_combine_segments(ctx, cur, None, sptr, n_seg, dst, st)
+                cur, nxt, sptr = dst, dst + n_seg * nb, sptr + seg.nbytes
+        elif dims is not None:
+            out_off, tables = self._grid_from_dims(dims, axes, final_shape)
+            obuf = DeviceBuffer(ctx, out_off.nbytes)
+            ctx.h2d(obuf.ptr, out_off, st)
+            tbuf = DeviceBuffer(ctx, max(tables["blob"].nbytes, 16))
+            ctx.h2d(tbuf.ptr, tables["blob"], st)
+            g = _lib.Grid()
+            g.ndim = ds.ndim
+            g.axes_mask = axes_mask
+            for d in range(ds.ndim):
+                g.n_coords[d] = tables["n_coords"][d]
+                g.out_extent[d] = final_shape[d] if d not in axes else 1
+                if d not in axes:
+                    g.pos_coord[d] = tbuf.ptr + 4 * tables["pos_coord"][d]
+                    g.pos_local[d] = tbuf.ptr + 4 * tables["pos_local"][d]
+                    g.coord_count[d] = tbuf.ptr + 4 * tables["coord_count"][d]
+            g.chunk_out_offsets = obuf.ptr
+            parts = DeviceBuffer(ctx, max(int(tables["n_parts"]), 1) * nb)
+            reduce_axes(obuf.ptr, parts.ptr)
+            engine.comoments_combine_grid(ctx, parts.ptr, g, fin.ptr, st)
+            keep += [obuf, tbuf, parts]
+        else:
+            sizes, fidx = [], []
+            for _, projs in chunk_list:
+                pos = [p.out_pos if i not in axes else np.zeros(1, dtype=np.int64) for i, p in enumerate(projs)]
+                grids = np.meshgrid(*pos, indexing="ij")
+                fidx.append(np.ravel_multi_index([x.reshape(-1) for x in grids], final_shape))
+                sizes.append(grids[0].size)
+            out_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+            f_all = np.concatenate(fidx)
+            order = np.argsort(f_all, kind="stable").astype(np.int64)
+            seg = np.searchsorted(f_all[order], np.arange(n_final + 1)).astype(np.int64)
+            meta = np.concatenate([out_off[:-1], order, seg])
+            mbuf = DeviceBuffer(ctx, meta.nbytes)
+            ctx.h2d(mbuf.ptr, meta, st)
+            parts = DeviceBuffer(ctx, max(int(out_off[-1]), 1) * nb)
+            reduce_axes(mbuf.ptr, parts.ptr)
+            engine.comoments_combine_segments(ctx, parts.ptr, mbuf.ptr + 8 * n, mbuf.ptr + 8 * (n + order.size),
+                                              n_final, fin.ptr, st)
+            keep += [mbuf, parts]
+        ctx.d2h(final, fin.ptr, st)
+        ctx.synchronize(st)
+        del keep, plan, plan_y
+        return fmt(final.reshape(final_shape))
+
     # -- histogram ------------------------------------------------------------------
     def _auto_range(self, index, compressor, filters):
         """``range=None``: the unmasked min and max of the selection as float64,
@@ -1439,6 +1631,20 @@ class Active:
                     "n": np.ma.MaskedArray(np.ascontiguousarray(parts["count"]),
                                            mask=np.zeros(parts.shape, dtype=bool))}
         return moments.finalize(parts, self._ddof, std=self._method == "std")
+
+    def _format_comoments(self, parts):
+        """The float64 result of a cov / corr query from its combined records
+        (comoments.finalize_cov / finalize_corr), or its components."""
+        if self._components:
+            empty = parts["count"] == 0
+            out = {name: np.ma.MaskedArray(np.ascontiguousarray(parts[name]), mask=empty)
+                   for name in ("mean_x", "mean_y", "m2_x", "m2_y", "cxy")}
+            out["n"] = np.ma.MaskedArray(np.ascontiguousarray(parts["count"]),
+                                         mask=np.zeros(parts.shape, dtype=bool))
+            return out
+        if self._method == "corr":
+            return comoments.finalize_corr(parts)
+        return comoments.finalize_cov(parts, self._ddof)
 
     def _format_weighted(self, parts):
         """The float64 result of a weighted mean / sum query from its combined

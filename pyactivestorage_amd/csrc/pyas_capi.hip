@@ -1573,6 +1573,116 @@ int pyas_moments_combine_grid(pyas_ctx *ctx, const pyas_moments *in, const pyas_
     return PYAS_OK;
 }
 
+int pyas_comoments_axes(pyas_ctx *ctx, const pyas_batch *bx, const pyas_mask *mask_x, const pyas_batch *by,
+                        const pyas_mask *mask_y, uint32_t axes_mask, const int64_t *out_offsets,
+                        pyas_comoments *out, void *stream) {
+    if (!ctx) return fail(PYAS_EINVAL, "ctx is NULL");
+    if (!bx || !by) return fail(PYAS_EINVAL, "batch is NULL");
+    if (bx->ndim < 1 || bx->ndim > PYAS_MAX_DIMS)
+        return fail(PYAS_ENOTSUP, "chunk rank %d outside 1..%d", bx->ndim, PYAS_MAX_DIMS);
+    // every check before any device call: the pairing first, then each side as pyas_moments_axes
+    if (by->ndim != bx->ndim) return fail(PYAS_EINVAL, "ranks differ: x %d, y %d", bx->ndim, by->ndim);
+    for (int d = 0; d < bx->ndim; ++d)
+        if (by->chunk_shape[d] != bx->chunk_shape[d])
+            return fail(PYAS_EINVAL, "chunk_shape[%d] differs: x %lld, y %lld", d, (long long)bx->chunk_shape[d],
+                        (long long)by->chunk_shape[d]);
+    if (by->n_chunks != bx->n_chunks)
+        return fail(PYAS_EINVAL, "n_chunks differs: x %lld, y %lld", (long long)bx->n_chunks, (long long)by->n_chunks);
+    if (by->dtype != bx->dtype) return fail(PYAS_ENOTSUP, "dtypes differ: x %d, y %d", bx->dtype, by->dtype);
+    pyas::ComomentsArgs x;
+    std::memset(&x, 0, sizeof(x));
+    int es, es_y;
+    bool shx, shy, bsx, bsy, mx, my;
+    int rc = prepare(ctx, bx, mask_x, x.x, es, shx, bsx, mx);
+    if (rc) return rc;
+    rc = prepare(ctx, by, mask_y, x.y, es_y, shy, bsy, my);
+    if (rc) return rc;
+    if (axes_mask >> bx->ndim) return fail(PYAS_EINVAL, "axes mask 0x%x beyond rank %d", axes_mask, bx->ndim);
+    const int64_t n = bx->n_chunks;
+    if (n == 0) return PYAS_OK;
+    if (!out) return fail(PYAS_EINVAL, "out is NULL");
+    PYAS_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    x.axes = axes_mask;
+    x.out_offsets = out_offsets;
+    x.out = out;
+    x.bswap_x = bsx;
+    x.bswap_y = bsy;
+    x.masked_x = mx;
+    x.masked_y = my;
+    x.shuf_x = shx;
+    x.shuf_y = shy;
+    if (axes_mask == (1u << bx->ndim) - 1u) {
+        // every dim reduced: a workgroup per (chunk, tile) of one side's bytes; tiles merge in tile order
+        const int64_t tpc = tiles_per_chunk(ctx, x.x.chunk_elems * es);
+        const int64_t grid = n * tpc;
+        if (grid >= (int64_t(1) << 31)) return fail(PYAS_ENOTSUP, "grid of %lld workgroups", (long long)grid);
+        x.bpc = tpc;
+        if (tpc > 1) {
+            void *scr = nullptr;
+            rc = ensure_scratch(ctx, stream, (size_t)grid * sizeof(pyas_comoments), &scr);
+            if (rc) return rc;
+            x.tiles = (pyas_comoments *)scr;
+        }
+        PYAS_HIP(pyas::launch_comoments_full(bx->dtype, x, grid, st));
+        if (tpc > 1) PYAS_HIP(pyas::launch_comoments_tiles(x.tiles, tpc, n, out_offsets, out, st));
+        return PYAS_OK;
+    }
+    if (!out_offsets) return fail(PYAS_EINVAL, "out_offsets is NULL");
+    int64_t keep_elems = 1;
+    for (int d = 0; d < bx->ndim; ++d)
+        if (!((axes_mask >> d) & 1u)) keep_elems *= bx->chunk_shape[d];
+    x.row = ((axes_mask >> (bx->ndim - 1)) & 1u) != 0;
+    // outputs per workgroup pass, as in pyas_moments_axes
+    const int64_t per_block = x.row ? (pyas::kBlock / pyas::kWave) * 16 : pyas::kBlock;
+    int64_t bpc = (keep_elems + per_block - 1) / per_block;
+    if (bpc > 64) bpc = 64;
+    if (bpc < 1) bpc = 1;
+    x.bpc = bpc;
+    const int64_t grid = n * bpc;
+    if (grid >= (int64_t(1) << 31)) return fail(PYAS_ENOTSUP, "grid too large");
+    PYAS_HIP(pyas::launch_comoments_axes(bx->dtype, x, grid, st));
+    return PYAS_OK;
+}
+
+int pyas_comoments_combine_segments(pyas_ctx *ctx, const pyas_comoments *in, const int64_t *index,
+                                    const int64_t *seg_offsets, int64_t n_segments, pyas_comoments *out,
+                                    void *stream) {
+    if (!ctx) return fail(PYAS_EINVAL, "ctx is NULL");
+    if (n_segments < 0) return fail(PYAS_EINVAL, "negative segment count");
+    if (n_segments == 0) return PYAS_OK;
+    if (!in || !seg_offsets || !out) return fail(PYAS_EINVAL, "NULL argument");
+    PYAS_HIP(hipSetDevice(ctx->device));
+    PYAS_HIP(pyas::launch_comoments_segments(in, index, seg_offsets, n_segments, out, (hipStream_t)stream));
+    return PYAS_OK;
+}
+
+int pyas_comoments_combine_grid(pyas_ctx *ctx, const pyas_comoments *in, const pyas_grid *g, pyas_comoments *out,
+                                void *stream) {
+    if (!ctx) return fail(PYAS_EINVAL, "ctx is NULL");
+    if (!g) return fail(PYAS_EINVAL, "grid is NULL");
+    if (g->ndim < 1 || g->ndim > PYAS_MAX_DIMS)
+        return fail(PYAS_ENOTSUP, "grid rank %d outside 1..%d", g->ndim, PYAS_MAX_DIMS);
+    if (g->axes_mask >> g->ndim) return fail(PYAS_EINVAL, "axes mask 0x%x beyond rank %d", g->axes_mask, g->ndim);
+    // (the checks of pyas_moments_combine_grid)
+    int64_t n_out = 1, n_layers = 1;
+    for (int d = 0; d < g->ndim; ++d) {
+        if (g->n_coords[d] < 1) return fail(PYAS_EINVAL, "n_coords[%d] = %lld", d, (long long)g->n_coords[d]);
+        if ((g->axes_mask >> d) & 1u) {
+            n_layers *= g->n_coords[d];
+        } else {
+            if (g->out_extent[d] < 1) return fail(PYAS_EINVAL, "out_extent[%d] = %lld", d, (long long)g->out_extent[d]);
+            if (!g->pos_coord[d] || !g->pos_local[d] || !g->coord_count[d])
+                return fail(PYAS_EINVAL, "kept dim %d has a NULL table", d);
+            n_out *= g->out_extent[d];
+        }
+    }
+    if (!in || !out || !g->chunk_out_offsets) return fail(PYAS_EINVAL, "NULL argument");
+    PYAS_HIP(hipSetDevice(ctx->device));
+    PYAS_HIP(pyas::launch_comoments_grid(in, *g, n_out, n_layers, out, (hipStream_t)stream));
+    return PYAS_OK;
+}
+
 int pyas_wsum_axes(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask, const pyas_weights *weights,
                    uint32_t axes_mask, const int64_t *out_offsets, pyas_wsum *out, void *stream) {
     if (!ctx) return fail(PYAS_EINVAL, "ctx is NULL");

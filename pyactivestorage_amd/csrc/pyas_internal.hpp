@@ -274,6 +274,26 @@ hipError_t launch_moments_segments(const pyas_moments *in, const int64_t *index,
                                    int64_t n_seg, pyas_moments *out, hipStream_t st);
 hipError_t launch_moments_grid(const pyas_moments *in, const pyas_grid &g, int64_t n_out, int64_t n_layers,
                                pyas_moments *out, hipStream_t st);
+// co-moments of two variables (pyas_comoments.hip): count / means / m2s / cxy records
+struct ComomentsArgs {
+    ReduceArgs x;                     // x.out unused; the geometry and the selection of both sides
+    ReduceArgs y;                     // data, offsets, mask and tab only
+    uint32_t axes;                    // reduced dims
+    int64_t bpc;                      // workgroups per chunk (full: tiles per chunk)
+    const int64_t *out_offsets;       // NULL (full only): chunk c's record at out[c]
+    pyas_comoments *out;
+    pyas_comoments *tiles;            // full with bpc > 1: one record per workgroup
+    bool bswap_x, bswap_y, masked_x, masked_y, shuf_x, shuf_y;
+    bool row;                         // innermost dim reduced: a wave per output
+};
+hipError_t launch_comoments_full(int dtype, const ComomentsArgs &a, int64_t grid, hipStream_t st);
+hipError_t launch_comoments_axes(int dtype, const ComomentsArgs &a, int64_t grid, hipStream_t st);
+hipError_t launch_comoments_tiles(const pyas_comoments *tiles, int64_t tpc, int64_t n_chunks,
+                                  const int64_t *out_offsets, pyas_comoments *out, hipStream_t st);
+hipError_t launch_comoments_segments(const pyas_comoments *in, const int64_t *index, const int64_t *seg,
+                                     int64_t n_seg, pyas_comoments *out, hipStream_t st);
+hipError_t launch_comoments_grid(const pyas_comoments *in, const pyas_grid &g, int64_t n_out, int64_t n_layers,
+                                 pyas_comoments *out, hipStream_t st);
 // weighted sums (pyas_weighted.hip): count / sum w / sum w x records
 struct WsumArgs {
     ReduceArgs r;                     // r.out unused

@@ -1,5 +1,6 @@
-// pyas_records.hpp — the three combines of 32-byte f64 records, written over
-// the record and its merge.  The weighted sums (pyas_weighted.hip) use them;
+// pyas_records.hpp — the three combines of f64 records, written over the
+// record and its merge.  The weighted sums (pyas_weighted.hip, 32 bytes) and
+// the co-moments (pyas_comoments.hip, 48 bytes) use them;
 // pyas_moments.hip keeps its own copies of the same walks (k_moments_tiles,
 // k_moments_segments, k_moments_grid), which can move here unchanged.
 // One thread per output folds its records sequentially in a fixed order: tiles

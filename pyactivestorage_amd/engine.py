@@ -27,6 +27,9 @@ def partial_dtype(dt) -> np.dtype:
 
 # Host view of ``pyas_moments`` (every storage dtype: the record is f64)
 moments_dtype = np.dtype([("count", "<i8"), ("mean", "<f8"), ("m2", "<f8"), ("reserved", "<u8")])
+# Host view of ``pyas_comoments``
+comoments_dtype = np.dtype([("count", "<i8"), ("mean_x", "<f8"), ("mean_y", "<f8"), ("m2_x", "<f8"),
+                            ("m2_y", "<f8"), ("cxy", "<f8")])
 
 # Host view of ``pyas_wsum``
 wsum_dtype = np.dtype([("count", "<i8"), ("sw", "<f8"), ("swx", "<f8"), ("reserved", "<u8")])
@@ -236,6 +239,27 @@ def moments_combine_segments(ctx: Context, in_ptr, index_ptr, seg_ptr, n_seg, ou
 def moments_combine_grid(ctx: Context, in_ptr, grid: _lib.Grid, out_ptr, stream) -> None:
     _lib.check(ctx.lib.pyas_moments_combine_grid(ctx.handle, in_ptr, ctypes.byref(grid), out_ptr, stream),
                "pyas_moments_combine_grid")
+
+
+def comoments_axes(ctx: Context, batch_x: _lib.Batch, mask_x: _lib.Mask, batch_y: _lib.Batch, mask_y: _lib.Mask,
+                   axes_mask: int, out_offsets_ptr, out_ptr, stream) -> None:
+    """pyas_comoments_axes: count / means / m2s / cxy records per chunk output
+    of the pairs of two variables (chunk c of ``batch_y`` against chunk c of
+    ``batch_x``, under ``batch_x``'s selection); outputs as :func:`moments_axes`'."""
+    _lib.check(ctx.lib.pyas_comoments_axes(ctx.handle, ctypes.byref(batch_x), ctypes.byref(mask_x),
+                                           ctypes.byref(batch_y), ctypes.byref(mask_y), int(axes_mask),
+                                           out_offsets_ptr, out_ptr, stream), "pyas_comoments_axes")
+
+
+def comoments_combine_segments(ctx: Context, in_ptr, index_ptr, seg_ptr, n_seg, out_ptr, stream) -> None:
+    """pyas_comoments_combine_segments (``index_ptr`` None: the identity)."""
+    _lib.check(ctx.lib.pyas_comoments_combine_segments(ctx.handle, in_ptr, index_ptr, seg_ptr, int(n_seg), out_ptr,
+                                                       stream), "pyas_comoments_combine_segments")
+
+
+def comoments_combine_grid(ctx: Context, in_ptr, grid: _lib.Grid, out_ptr, stream) -> None:
+    _lib.check(ctx.lib.pyas_comoments_combine_grid(ctx.handle, in_ptr, ctypes.byref(grid), out_ptr, stream),
+               "pyas_comoments_combine_grid")
 
 
 def hist_axes(ctx: Context, batch: _lib.Batch, mask: _lib.Mask, edges_ptr, n_bins: int, uniform, axes_mask: int,
