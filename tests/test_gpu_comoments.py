@@ -535,3 +535,84 @@ def test_entry_point_errors(gpu):
     g.ndim = 0
     assert gpu.lib.pyas_comoments_combine_grid(gpu.handle, 8, ctypes.byref(g), 8, None) == _lib.ENOTSUP
     assert gpu.lib.pyas_comoments_combine_segments(gpu.handle, None, None, None, 1, None, None) == _lib.EINVAL
+
+
+# -- 11. branches the shapes above do not reach (the cases of tests/_stats_gaps.py) -----------
+from tests import _stats_gaps as G   # noqa: E402
+
+MASKED = pytest.mark.parametrize("masked", [False, True], ids=["plain", "masked"])
+LAYOUTS = {"xshuf": (True, False), "yshuf": (False, True), "both": (True, True), "plain": (False, False)}
+
+
+@functools.lru_cache(maxsize=None)
+def gap_vars(group, name, dt="<f4", masked=False, layout=None):
+    """The case's pair; masked: the two sides have their fill values at different positions."""
+    x, y, ax, ay = G.pair(group, name, dt, masked)
+    _, chunks, _, _, shuffled = G.case(group, name)
+    sx, sy = LAYOUTS[layout or ("both" if shuffled else "plain")]
+    return (x, y, ax, ay, make_var(x, chunks, ax, shuffle=sx, pad=G.fill_of(ax, dt)),
+            make_var(y, chunks, ay, shuffle=sy, pad=G.fill_of(ay, dt)))
+
+
+def gap_check(group, name, dt, masked, iname, axis, layout=None):
+    x, y, ax, ay, vx, vy = gap_vars(group, name, dt, masked, layout)
+    index = G.index_of(group, name, iname)
+    o = oracle(x, y, ax, ay, index, axis)
+    what = f"{group} {name} {dt} {layout or ''} {iname} {G.axis_id(axis)}"
+    check(query(vx, vy, "cov", axis, 1, index), o, "cov", 1, what)
+    check(query(vx, vy, "corr", axis, 0, index), o, "corr", 0, what)
+
+
+@MASKED
+@pytest.mark.parametrize("name,iname", [(n, i) for n in G.G1 for i in G.case("G1", n)[3]])
+def test_g1_reduced_positions_beyond_the_offset_map(gpu, name, iname, masked):
+    """More than kComRoff reduced positions in a chunk: the radix-counter walk
+    of k_comoments_axes, a wave ("row") and a lane ("lane") per output."""
+    gap_check("G1", name, "<f4", masked, iname, G.case("G1", name)[2][0])
+
+
+@MASKED
+@pytest.mark.parametrize("name", list(G.G2))
+def test_g2_second_trip_of_the_lane_loop(gpu, name, masked):
+    """16,900 kept outputs in a chunk, 16,384 lanes in its launch."""
+    x, y, ax, ay, vx, vy = gap_vars("G2", name, "<f4", masked)
+    k = G.G2_SECOND_TRIP
+    o = oracle(x, y, ax, ay, Ellipsis, (0,))
+    tail = {key: v.reshape(-1)[k:] for key, v in o.items()}
+    for method, ddof in (("cov", 1), ("corr", 0)):
+        got = query(vx, vy, method, (0,), ddof, Ellipsis)
+        assert got.shape == (1, 130, 130)
+        check(got.reshape(-1)[k:], tail, method, ddof, f"G2 {name}: the second trip, outputs {k}..16899")
+        check(got, o, method, ddof, f"G2 {name}: every output")
+
+
+@MASKED
+@pytest.mark.parametrize("axis", [None, (0,), (2,)], ids=G.axis_id)
+@pytest.mark.parametrize("layout", ["xshuf", "yshuf", "both"])
+@pytest.mark.parametrize("dt", G.G3_DTYPES)
+def test_g3_shuffled_chunks_of_odd_size(gpu, dt, layout, axis, masked):
+    """Shuffled chunks of 105 elements on either side or both: the
+    per-element fallback of the shuffled co-moment runs."""
+    for iname in ("whole", "from1"):
+        gap_check("G3", "odd", dt, masked, iname, axis, layout)
+
+
+@pytest.mark.parametrize("iname", list(G.G3_RUNS))
+@pytest.mark.parametrize("layout", ["xshuf", "yshuf", "both"])
+@pytest.mark.parametrize("dt", G.G3_DTYPES)
+def test_g3_runs_inside_a_shuffled_chunk(gpu, dt, layout, iname):
+    gap_check("G3", "runs", dt, False, iname, None, layout)
+
+
+@MASKED
+@pytest.mark.parametrize("name", list(G.G4))
+def test_g4_ranks(gpu, name, masked):
+    for iname, _, axis, _ in G.combos("G4", name):
+        gap_check("G4", name, "<f4", masked, iname, axis)
+
+
+@MASKED
+@pytest.mark.parametrize("dt,shuffle", G.G5_LAYOUTS, ids=lambda v: {False: "plain", True: "shuffled"}.get(v, v))
+def test_g5_dtypes(gpu, dt, shuffle, masked):
+    for axis in (None, (1,)):
+        gap_check("G5", "dtypes", dt, masked, "whole", axis, "both" if shuffle else "plain")

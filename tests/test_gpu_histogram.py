@@ -486,3 +486,109 @@ def test_errors(gpu, monkeypatch):
     got = Active(var).histogram(4, (250, 300), axis=(1,))[...]
     same(got, oracle(data, attrs, (Ellipsis,), (1,), H.edges(4, (250, 300)))["counts"])
     assert H.TABLE_CAP_BYTES == 15 * 37 * 7 * 8
+
+
+# -- 11. branches the shapes above do not reach (the cases of tests/_stats_gaps.py) -----------
+from tests import _stats_gaps as G   # noqa: E402
+
+MASKED = pytest.mark.parametrize("masked", [False, True], ids=["plain", "masked"])
+
+
+def gap_range(dt):
+    if dt in G.G5_HIST_RANGE:
+        return G.G5_HIST_RANGE[dt]
+    return G.HIST_RANGE if np.dtype(dt).kind == "f" else (-1500, 1500)     # <i2 over -3000..3000
+
+
+@functools.lru_cache(maxsize=None)
+def gap_var(group, name, dt="<f4", masked=False, shuffle=None):
+    """The case's data with every edge of its 4 bins planted (rounded to the
+    dtype, with both neighbours); the data's spread lies on both sides of the range."""
+    data, attrs = G.single(group, name, dt, masked)
+    _, chunks, _, _, shuffled = G.case(group, name)
+    shuffle = shuffled if shuffle is None else shuffle
+    rng = gap_range(dt)
+    e = H.edges(G.HIST_BINS, rng)
+    data = G.planted(data, attrs, plant_values(dt, e))
+    return data, attrs, make_var(data, chunks, attrs, shuffle=shuffle, pad=G.fill_of(attrs, dt)), rng, e
+
+
+def gap_check(group, name, dt, masked, iname, axis, shuffle=None):
+    data, attrs, var, rng, e = gap_var(group, name, dt, masked, shuffle)
+    index = G.index_of(group, name, iname)
+    want = oracle(data, attrs, index, axis, e)
+    check(query(var, G.HIST_BINS, rng, axis, index, True), want, True, f"{group} {name} {dt} {iname} {G.axis_id(axis)}")
+    return want
+
+
+@MASKED
+@pytest.mark.parametrize("name", list(G.G2))
+def test_g2_second_trip_of_the_lane_loop(gpu, name, masked):
+    """16,900 kept outputs in a chunk, 16,384 lanes in its launch."""
+    data, attrs, var, rng, e = gap_var("G2", name, "<f4", masked)
+    k = G.G2_SECOND_TRIP
+    want = oracle(data, attrs, (Ellipsis,), (0,), e)
+    assert want["below"].sum() > 0 and want["above"].sum() > 0
+    got = query(var, G.HIST_BINS, rng, (0,), Ellipsis, True)
+    for key in ("n", "below", "above", "nan"):
+        same(got[key].reshape(-1)[k:], want[key].reshape(-1)[k:], f"G2 {name} {key}: the second trip, outputs {k}..16899")
+    same(got["counts"].reshape(-1, G.HIST_BINS)[k:], want["counts"].reshape(-1, G.HIST_BINS)[k:],
+         f"G2 {name} counts: the second trip, outputs {k}..16899")
+    check(got, want, True, f"G2 {name}: every output")
+
+
+@MASKED
+@pytest.mark.parametrize("iname", ["whole", "from1"])
+@pytest.mark.parametrize("axis", [None, (0,), (2,)], ids=G.axis_id)
+@pytest.mark.parametrize("dt", G.G3_DTYPES)
+def test_g3_shuffled_chunks_of_odd_size(gpu, dt, axis, iname, masked):
+    """Shuffled chunks of 105 elements: hist_run_shuffled's per-element fallback."""
+    want = gap_check("G3", "odd", dt, masked, iname, axis)
+    assert want["below"].sum() > 0 and want["above"].sum() > 0
+
+
+@pytest.mark.parametrize("iname", list(G.G3_RUNS))
+@pytest.mark.parametrize("dt", G.G3_DTYPES)
+def test_g3_runs_inside_a_shuffled_chunk(gpu, dt, iname):
+    gap_check("G3", "runs", dt, False, iname, None)
+
+
+@MASKED
+def test_g4_rank_8(gpu, masked):
+    for iname, _, axis, _ in G.combos("G4", "8d"):
+        want = gap_check("G4", "8d", "<f4", masked, iname, axis)
+        assert want["below"].sum() > 0 and want["above"].sum() > 0
+
+
+@MASKED
+@pytest.mark.parametrize("dt,shuffle", G.G5_LAYOUTS, ids=lambda v: {False: "plain", True: "shuffled"}.get(v, v))
+def test_g5_dtypes(gpu, dt, shuffle, masked):
+    for axis in (None, (1,)):
+        want = gap_check("G5", "dtypes", dt, masked, "whole", axis, shuffle)
+        assert want["below"].sum() > 0 and want["above"].sum() > 0
+        assert (want["counts"].reshape(-1, G.HIST_BINS).sum(axis=0) > 0).all()
+
+
+@pytest.mark.parametrize("dt,off", G.G6_CASES)
+def test_g6_base_misaligned(gpu, dt, off):
+    """One chunk ``off`` bytes into its buffer, every dim reduced, through
+    pyas_hist_axes itself: the head and tail of hist_run_plain."""
+    from pyactivestorage_amd import engine
+    from pyactivestorage_amd.device import DeviceBuffer
+    rng = G.HIST_RANGE if dt == "<f4" else (64, 192)
+    e = H.edges(G.HIST_BINS, rng)
+    data = G.planted(G.g6_chunk(dt), None, plant_values(dt, e))
+    for iname, index in G.G6_INDEXES.items():
+        st, buf, plan = G.misaligned_plan(gpu, data, off, index)
+        ebuf, tbuf = DeviceBuffer(gpu, e.nbytes), DeviceBuffer(gpu, (G.HIST_BINS + 3) * 8)
+        gpu.h2d(ebuf.ptr, e, st)
+        engine.hist_reset(gpu, tbuf.ptr, 1, G.HIST_BINS, st)
+        engine.hist_axes(gpu, plan.batch, plan.mask_up.struct, ebuf.ptr, G.HIST_BINS,
+                         (e[0], G.HIST_BINS / (e[-1] - e[0])), 0b111, None, None, tbuf.ptr, st)
+        tab = np.full((1, G.HIST_BINS + 3), -1, np.int64)
+        gpu.d2h(tab, tbuf.ptr, st)
+        gpu.synchronize(st)
+        cnt, below, above, nan = H.bin_counts(data[Ellipsis if index is None else index].astype(np.float64), e)
+        want = np.concatenate([cnt, [below, above, nan]]).astype(np.int64).reshape(1, -1)
+        assert below > 0 and above > 0 and (cnt > 0).all()
+        same(tab, want, f"G6 {dt} offset {off} {iname}")

@@ -385,3 +385,95 @@ def test_entry_point_errors(gpu):
     table[0, 0] = (2, 1, 4)
     with pytest.raises(IndexError):
         ReductionPlan(gpu, "<f4", (4, 4), 0, np.zeros(1, np.int64), sel_table=table, missing=(None,) * 4)
+
+
+# -- 10. branches the shapes above do not reach (the cases of tests/_stats_gaps.py) -----------
+from tests import _stats_gaps as G   # noqa: E402
+
+BOTH = (("var", 0), ("std", 1))
+MASKED = pytest.mark.parametrize("masked", [False, True], ids=["plain", "masked"])
+
+
+@functools.lru_cache(maxsize=None)
+def gap_var(group, name, dt="<f4", masked=False, shuffle=None):
+    data, attrs = G.single(group, name, dt, masked)
+    _, chunks, _, _, shuffled = G.case(group, name)
+    shuffle = shuffled if shuffle is None else shuffle
+    return data, attrs, make_var(data, chunks, attrs, shuffle=shuffle, pad=G.fill_of(attrs, dt))
+
+
+def gap_check(group, name, dt, masked, iname, axis, shuffle=None):
+    data, attrs, var = gap_var(group, name, dt, masked, shuffle)
+    index = G.index_of(group, name, iname)
+    for method, ddof in BOTH:
+        check(query(var, method, axis, ddof, index), oracle(data, attrs, index, axis, method, ddof),
+              f"{group} {name} {dt} {iname} {G.axis_id(axis)} {method}")
+
+
+@MASKED
+@pytest.mark.parametrize("name,iname", [(n, i) for n in G.G1 for i in G.case("G1", n)[3]])
+def test_g1_reduced_positions_beyond_the_offset_map(gpu, name, iname, masked):
+    """More than kMomRoff reduced positions in a chunk: the radix-counter walk
+    of k_moments_axes, a wave ("row") and a lane ("lane") per output."""
+    gap_check("G1", name, "<f4", masked, iname, G.case("G1", name)[2][0])
+
+
+@MASKED
+@pytest.mark.parametrize("name", list(G.G2))
+def test_g2_second_trip_of_the_lane_loop(gpu, name, masked):
+    """16,900 kept outputs in a chunk, 16,384 lanes in its launch."""
+    data, attrs, var = gap_var("G2", name, "<f4", masked)
+    k = G.G2_SECOND_TRIP
+    for method, ddof in BOTH:
+        got, want = query(var, method, (0,), ddof, Ellipsis), oracle(data, attrs, Ellipsis, (0,), method, ddof)
+        assert got.shape == want.shape == (1, 130, 130)
+        check(got.reshape(-1)[k:], want.reshape(-1)[k:], f"G2 {name} {method}: the second trip, outputs {k}..16899")
+        check(got, want, f"G2 {name} {method}: every output")
+
+
+@MASKED
+@pytest.mark.parametrize("iname", ["whole", "from1"])
+@pytest.mark.parametrize("axis", [None, (0,), (2,)], ids=G.axis_id)
+@pytest.mark.parametrize("dt", G.G3_DTYPES)
+def test_g3_shuffled_chunks_of_odd_size(gpu, dt, axis, iname, masked):
+    """Shuffled chunks of 105 elements: mom_run_shuffled's per-element fallback."""
+    gap_check("G3", "odd", dt, masked, iname, axis)
+
+
+@pytest.mark.parametrize("iname", list(G.G3_RUNS))
+@pytest.mark.parametrize("dt", G.G3_DTYPES)
+def test_g3_runs_inside_a_shuffled_chunk(gpu, dt, iname):
+    gap_check("G3", "runs", dt, False, iname, None)
+
+
+@MASKED
+@pytest.mark.parametrize("name", list(G.G4))
+def test_g4_ranks(gpu, name, masked):
+    for iname, _, axis, _ in G.combos("G4", name):
+        gap_check("G4", name, "<f4", masked, iname, axis)
+
+
+@MASKED
+@pytest.mark.parametrize("dt,shuffle", G.G5_LAYOUTS, ids=lambda v: {False: "plain", True: "shuffled"}.get(v, v))
+def test_g5_dtypes(gpu, dt, shuffle, masked):
+    for axis in (None, (1,)):
+        gap_check("G5", "dtypes", dt, masked, "whole", axis, shuffle)
+
+
+@pytest.mark.parametrize("dt,off", G.G6_CASES)
+def test_g6_base_misaligned(gpu, dt, off):
+    """One chunk ``off`` bytes into its buffer, every dim reduced, through
+    pyas_moments_axes itself: the head and tail of mom_run_plain."""
+    from pyactivestorage_amd import engine
+    from pyactivestorage_amd.device import DeviceBuffer
+    data = G.g6_chunk(dt)
+    for iname, index in G.G6_INDEXES.items():
+        st, buf, plan = G.misaligned_plan(gpu, data, off, index)
+        out = np.zeros(1, engine.moments_dtype)
+        obuf = DeviceBuffer(gpu, out.nbytes)
+        engine.moments_axes(gpu, plan.batch, plan.mask_up.struct, 0b111, None, obuf.ptr, st)
+        gpu.d2h(out, obuf.ptr, st)
+        gpu.synchronize(st)
+        want = oracle(data, None, Ellipsis if index is None else index, None, "var", 0)
+        assert int(out["count"][0]) == data[Ellipsis if index is None else index].size
+        check(moments.finalize(out.reshape(1, 1, 1)), want, f"G6 {dt} offset {off} {iname}")

@@ -334,3 +334,107 @@ def test_same_bytes_twice(gpu):
         for k in ("quantile", "n", "nan"):
             assert np.ma.getdata(a[k]).tobytes() == np.ma.getdata(b[k]).tobytes()
         assert np.array_equal(np.ma.getmaskarray(a["quantile"]), np.ma.getmaskarray(b["quantile"]))
+
+
+# -- 11. branches the shapes above do not reach (the cases of tests/_stats_gaps.py) -----------
+from tests import _stats_gaps as G   # noqa: E402
+
+MASKED = pytest.mark.parametrize("masked", [False, True], ids=["plain", "masked"])
+
+
+@functools.lru_cache(maxsize=None)
+def gap_var(group, name, dt="<f4", masked=False, shuffle=None):
+    data, attrs = G.single(group, name, dt, masked)
+    _, chunks, _, _, shuffled = G.case(group, name)
+    shuffle = shuffled if shuffle is None else shuffle
+    return data, attrs, make_var(data, chunks, attrs, shuffle=shuffle, pad=G.fill_of(attrs, dt))
+
+
+def gap_check(group, name, dt, masked, iname, axis, shuffle=None):
+    data, attrs, var = gap_var(group, name, dt, masked, shuffle)
+    index = G.index_of(group, name, iname)
+    check(query(var, G.QS, axis, index, True), oracle(data, attrs, index, axis, G.QS), True,
+          f"{group} {name} {dt} {iname} {G.axis_id(axis)}")
+
+
+@MASKED
+@pytest.mark.parametrize("name", list(G.G2))
+def test_g2_second_trip_of_the_lane_loop(gpu, name, masked):
+    """16,900 kept outputs in a chunk, 16,384 lanes in its launch."""
+    data, attrs, var = gap_var("G2", name, "<f4", masked)
+    k = G.G2_SECOND_TRIP
+    want = oracle(data, attrs, (Ellipsis,), (0,), G.QS)
+    got = query(var, G.QS, (0,), Ellipsis, True)
+    what = f"G2 {name}: the second trip, outputs {k}..16899"
+    for key in ("n", "nan"):
+        assert np.array_equal(got[key].reshape(-1)[k:], want[key].reshape(-1)[k:]), (what, key)
+    same_masked(got["quantile"].reshape(-1, len(G.QS))[k:], want["quantile"].reshape(-1, len(G.QS))[k:], what)
+    check(got, want, True, f"G2 {name}: every output")
+
+
+@MASKED
+@pytest.mark.parametrize("iname", ["whole", "from1"])
+@pytest.mark.parametrize("axis", [None, (0,), (2,)], ids=G.axis_id)
+@pytest.mark.parametrize("dt", G.G3_DTYPES)
+def test_g3_shuffled_chunks_of_odd_size(gpu, dt, axis, iname, masked):
+    """Shuffled chunks of 105 elements: hist_run_shuffled's per-element
+    fallback under the digit counts."""
+    gap_check("G3", "odd", dt, masked, iname, axis)
+
+
+@pytest.mark.parametrize("iname", list(G.G3_RUNS))
+@pytest.mark.parametrize("dt", G.G3_DTYPES)
+def test_g3_runs_inside_a_shuffled_chunk(gpu, dt, iname):
+    gap_check("G3", "runs", dt, False, iname, None)
+
+
+@MASKED
+@pytest.mark.parametrize("name", list(G.G4))
+def test_g4_ranks(gpu, name, masked):
+    for iname, _, axis, _ in G.combos("G4", name):
+        gap_check("G4", name, "<f4", masked, iname, axis)
+
+
+# (test_dtypes has <u8, and >f4 for a swapped type: the types it leaves out)
+@MASKED
+@pytest.mark.parametrize("dt,shuffle", [(dt, sh) for dt, sh in G.G5_LAYOUTS if dt != "<u8"],
+                         ids=lambda v: {False: "plain", True: "shuffled"}.get(v, v))
+def test_g5_dtypes(gpu, dt, shuffle, masked):
+    for axis in (None, (1,)):
+        gap_check("G5", "dtypes", dt, masked, "whole", axis, shuffle)
+
+
+@pytest.mark.parametrize("dt,off", G.G6_CASES)
+def test_g6_base_misaligned(gpu, dt, off):
+    """One chunk ``off`` bytes into its buffer, every dim reduced, through
+    pyas_select_axes itself: the key's first digit, then a digit below it
+    under a prefix (f4: the fullest first digit's next 8 bits; u1, whose key
+    is the value: the last 8 bits), against the counts of quantile.keys."""
+    from pyactivestorage_amd import engine
+    from pyactivestorage_amd.device import DeviceBuffer
+    data = G.g6_chunk(dt, spread=True)
+    for iname, index in G.G6_INDEXES.items():
+        st, buf, plan = G.misaligned_plan(gpu, data, off, index)
+        keys = Q.keys(data[Ellipsis if index is None else index].reshape(-1)).astype(np.uint64)
+        first = np.bincount((keys >> np.uint64(24)).astype(np.int64), minlength=256)
+        top = int(first.argmax())
+        shift = 16 if dt == "<f4" else 0
+        assert (first > 0).sum() >= (8 if dt == "<f4" else 1) and first[top] > 256
+        tbuf, pbuf = DeviceBuffer(gpu, (256 + 3) * 8), DeviceBuffer(gpu, 16)
+        gpu.h2d(pbuf.ptr, np.array([top, 0], np.uint64), st)
+        for prefix_ptr, sh in ((None, 24), (pbuf.ptr, shift)):
+            engine.hist_reset(gpu, tbuf.ptr, 1, 256, st)
+            engine.select_axes(gpu, plan.batch, plan.mask_up.struct, prefix_ptr, sh, 8, 0b111, None, None, tbuf.ptr, st)
+            tab = np.full(256 + 3, -1, np.int64)
+            gpu.d2h(tab, tbuf.ptr, st)
+            gpu.synchronize(st)
+            want = np.zeros(256 + 3, np.int64)
+            if prefix_ptr is None:
+                want[:256] = first
+            else:
+                hi = keys >> np.uint64(sh + 8)
+                on = hi == np.uint64(top)
+                want[:256] = np.bincount(((keys[on] >> np.uint64(sh)) & np.uint64(255)).astype(np.int64), minlength=256)
+                want[256], want[257] = (hi < np.uint64(top)).sum(), (hi > np.uint64(top)).sum()
+                assert (want[:256] > 0).sum() > 100
+            assert np.array_equal(tab, want), (f"G6 {dt} offset {off} {iname} shift {sh}", tab, want)

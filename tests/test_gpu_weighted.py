@@ -11,7 +11,7 @@ in different orders, ``u = 2^-53`` per operation.  For each output, with
 same without the division for a sum.  Masks, ``n`` and the positions with
 ``sum(w) == 0`` are exact; the dtype is float64; NaN where the oracle has NaN.
 (Each check prints its largest error as a fraction of the bound; on an MI355X
-the largest over this file was 0.084.)
+the largest over this file was 0.11.)
 """
 import ctypes
 import functools
@@ -524,3 +524,103 @@ def test_group_with_weights_not_implemented(gpu):
         a = Active(var, group=object())
         with pytest.raises(NotImplementedError, match="weights with group="):
             getattr(a, method)(weights=wset((1,)))[...]
+
+
+# -- 12. branches the shapes above do not reach (the cases of tests/_stats_gaps.py) -----------
+from tests import _stats_gaps as G   # noqa: E402
+
+MASKED = pytest.mark.parametrize("masked", [False, True], ids=["plain", "masked"])
+
+
+@functools.lru_cache(maxsize=None)
+def gap_var(group, name, dt="<f4", masked=False, shuffle=None):
+    data, attrs = G.single(group, name, dt, masked)
+    _, chunks, _, _, shuffled = G.case(group, name)
+    shuffle = shuffled if shuffle is None else shuffle
+    return data, attrs, make_var(data, chunks, attrs, shuffle=shuffle, pad=G.fill_of(attrs, dt))
+
+
+def gap_check(group, name, dt, masked, iname, axis, shuffle=None, dims=None):
+    data, attrs, var = gap_var(group, name, dt, masked, shuffle)
+    index = G.index_of(group, name, iname)
+    w = G.weights(data.shape, dims)
+    want = oracle(data, attrs, index, axis, w)
+    for method in ("mean", "sum"):
+        check(query(var, method, axis, w, index), want, method, f"{group} {name} {dt} {iname} {G.axis_id(axis)}")
+
+
+@MASKED
+@pytest.mark.parametrize("name", list(G.G2))
+def test_g2_second_trip_of_the_lane_loop(gpu, name, masked):
+    """16,900 kept outputs in a chunk, 16,384 lanes in its launch."""
+    data, attrs, var = gap_var("G2", name, "<f4", masked)
+    k = G.G2_SECOND_TRIP
+    w = G.weights(data.shape)
+    want = oracle(data, attrs, Ellipsis, (0,), w)
+    tail = tuple(v.reshape(-1)[k:] for v in want[:4]) + (want[4],)
+    for method in ("mean", "sum"):
+        got = query(var, method, (0,), w, Ellipsis)
+        assert got.shape == (1, 130, 130)
+        check(got.reshape(-1)[k:], tail, method, f"G2 {name}: the second trip, outputs {k}..16899")
+        check(got, want, method, f"G2 {name}: every output")
+
+
+@MASKED
+@pytest.mark.parametrize("iname", ["whole", "from1"])
+@pytest.mark.parametrize("axis", [None, (0,), (2,)], ids=G.axis_id)
+@pytest.mark.parametrize("dt", G.G3_DTYPES)
+@pytest.mark.parametrize("name", ["odd", "odd17"])
+def test_g3_shuffled_chunks_of_odd_size(gpu, name, dt, axis, iname, masked):
+    """Shuffled chunks of 105 elements (rows of 7: the full reduction walks)
+    and of 255 (rows of 17: ws_run_shuffled's per-element fallback)."""
+    gap_check("G3", name, dt, masked, iname, axis)
+
+
+@pytest.mark.parametrize("iname", list(G.G3_RUNS))
+@pytest.mark.parametrize("dt", G.G3_DTYPES)
+def test_g3_runs_inside_a_shuffled_chunk(gpu, dt, iname):
+    gap_check("G3", "runs", dt, False, iname, None)
+
+
+@MASKED
+def test_g4_rank_8(gpu, masked):
+    """PYAS_MAX_DIMS dims, weight vectors on the first and the last."""
+    for iname, _, axis, _ in G.combos("G4", "8d"):
+        gap_check("G4", "8d", "<f4", masked, iname, axis, dims=(0, 7))
+
+
+@MASKED
+@pytest.mark.parametrize("dt,shuffle", G.G5_LAYOUTS, ids=lambda v: {False: "plain", True: "shuffled"}.get(v, v))
+def test_g5_dtypes(gpu, dt, shuffle, masked):
+    for axis in (None, (1,)):
+        gap_check("G5", "dtypes", dt, masked, "whole", axis, shuffle)
+
+
+@pytest.mark.parametrize("dt,off", G.G6_CASES)
+def test_g6_base_misaligned(gpu, dt, off):
+    """One chunk ``off`` bytes into its buffer, every dim reduced, through
+    pyas_wsum_axes itself: the head and tail of ws_run_plain, and the position
+    its vectors' weights start from."""
+    from pyactivestorage_amd import engine
+    from pyactivestorage_amd.device import DeviceBuffer
+    data = G.g6_chunk(dt)
+    w = G.weights(data.shape)
+    pool = np.concatenate([w[0], w[1], w[2]])
+    origin = np.zeros((1, 8), np.int32)
+    origin[0, :3] = (0, data.shape[0], data.shape[0] + data.shape[1])
+    for iname, index in G.G6_INDEXES.items():
+        st, buf, plan = G.misaligned_plan(gpu, data, off, index)
+        out = np.zeros(1, engine.wsum_dtype)
+        obuf, zero = DeviceBuffer(gpu, out.nbytes), DeviceBuffer(gpu, 16)
+        wbuf, gbuf = DeviceBuffer(gpu, pool.nbytes), DeviceBuffer(gpu, origin.nbytes)
+        gpu.h2d(zero.ptr, np.zeros(1, np.int64), st)
+        gpu.h2d(wbuf.ptr, pool, st)
+        gpu.h2d(gbuf.ptr, origin, st)
+        engine.wsum_axes(gpu, plan.batch, plan.mask_up.struct, wbuf.ptr, gbuf.ptr, 0b111, zero.ptr, obuf.ptr, st)
+        gpu.d2h(out, obuf.ptr, st)
+        gpu.synchronize(st)
+        want = oracle(data, None, Ellipsis if index is None else index, None, w)
+        out = out.reshape(1, 1, 1)
+        np.testing.assert_array_equal(out["count"], want[2])
+        check(weighted.finalize(out), want, "mean", f"G6 {dt} offset {off} {iname}")
+        check(weighted.finalize(out, mean=False), want, "sum", f"G6 {dt} offset {off} {iname}")
