@@ -595,6 +595,57 @@ int pyas_comoments_combine_segments(pyas_ctx *ctx, const pyas_comoments *in, con
 int pyas_comoments_combine_grid(pyas_ctx *ctx, const pyas_comoments *in, const pyas_grid *grid,
                                 pyas_comoments *out, void *stream);
 
+/* ---- least-squares trend against a coordinate (Active.trend) ----------------
+ * The pyas_comoments record with x a coordinate instead of a second stored
+ * variable: for an element of chunk c at index i inside the chunk along chunk
+ * dim `dim`, x = pool[origin[c] + i] and y is the data value (converted to f64
+ * as astype(float64) does); the pair counts when y is unmasked.  Slices,
+ * strides and index lists look up the same way (by the element's index inside
+ * the chunk).  Every coordinate of a chunk must be readable:
+ * pool[origin[c] .. + chunk_shape[dim]).  This is the single-dim form of
+ * pyas_weights.  Lanes accumulate and records merge exactly as for
+ * pyas_comoments_axes, so slope = cxy / m2_x, intercept = mean_y - slope mean_x,
+ * and pyas_comoments_combine_segments / _grid combine the records. */
+typedef struct {
+    const double *pool;      /* device: the coordinate vector, zero-padded to whole chunks */
+    const int32_t *origin;   /* device [n_chunks]: index in pool of chunk c's local index 0 along dim */
+    int32_t dim;             /* the chunk dim the coordinate runs along; must be in the reduced dims */
+} pyas_coord;
+
+/* pyas_comoments_axes against a coordinate: outputs, out_offsets and errors as
+ * there (out_offsets may be NULL only with every dim in axes_mask); PYAS_EINVAL
+ * when coord or one of its pointers is NULL or coord->dim is not a reduced dim.
+ * A per-element walk for any selection and mask: it has no speed target. */
+int pyas_trend_axes(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask,
+                    const pyas_coord *coord, uint32_t axes_mask, const int64_t *out_offsets,
+                    pyas_comoments *out, void *stream);
+/* The dense path of a box query: pyas_trend_axes + pyas_comoments_combine_grid
+ * in ONE launch that writes one finished record per final output (out, device,
+ * C order over grid->out_extent) and no per-chunk records.  The caller promises
+ * a unit-step box: every dim's selection is one unit-step range of the
+ * variable (batch->sel NULL: whole chunks), the chunks are laid out in the
+ * grid's C order (chunk n = grid position n, prod n_coords chunks) and chunks
+ * that share a dim's chunk coordinate share that dim's selection.  Only
+ * grid->ndim, axes_mask, n_coords and out_extent are read.  The reduced dims
+ * must be a leading prefix 0 .. P-1 of the dims with at least one kept dim
+ * behind them, and the mask must have no vector tables: otherwise
+ * PYAS_ENOTSUP, nothing is launched and the caller takes pyas_trend_axes.
+ * A lane owns 4 consecutive outputs along the innermost dim and walks them
+ * through every row of every chunk layer in increasing index order, so a
+ * record is the lane's own sums (nothing is merged).  Records differ from the
+ * two-step path's in the last bits (another summation order); both are
+ * bit-identical from run to run. */
+int pyas_trend_cols(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask,
+                    const pyas_coord *coord, const pyas_grid *grid, pyas_comoments *out,
+                    void *stream);
+/* value[i] = cxy / m2_x (PYAS_TREND_SLOPE) or mean_y - slope mean_x
+ * (PYAS_TREND_INTERCEPT, one fma) of record i, masked[i] = (count == 0), all
+ * device: 9 bytes per output cross PCIe instead of 48.  A masked value is 0;
+ * m2_x == 0 gives NaN (0 / 0), unmasked. */
+enum { PYAS_TREND_SLOPE = 0, PYAS_TREND_INTERCEPT = 1 };
+int pyas_trend_finalize(pyas_ctx *ctx, const pyas_comoments *in, int64_t n, int32_t what,
+                        double *value, uint8_t *masked, void *stream);
+
 /* ---- weighted sums (Active.mean / Active.sum with weights=) -----------------
  * Partial record of a weighted mean over a set of elements (32 bytes):
  * count unmasked elements; sw = sum w; swx = sum w x  (f64).  The all-zero

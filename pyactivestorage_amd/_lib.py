@@ -60,6 +60,14 @@ class Weights(ctypes.Structure):
     _fields_ = [("pool", ctypes.c_void_p), ("origin", ctypes.c_void_p)]
 
 
+class Coord(ctypes.Structure):
+    """pyas_coord: the coordinate vector, each chunk's origin in it (device pointers) and its chunk dim."""
+    _fields_ = [("pool", ctypes.c_void_p), ("origin", ctypes.c_void_p), ("dim", ctypes.c_int32)]
+
+
+TREND_SLOPE, TREND_INTERCEPT = 0, 1
+
+
 class Hist(ctypes.Structure):
     """pyas_hist: device edges (n_bins + 1), PYAS_HIST_* flags and the uniform guess (lo, scale)."""
     _fields_ = [("edges", ctypes.c_void_p), ("n_bins", ctypes.c_int32), ("flags", ctypes.c_uint32),
@@ -250,6 +258,11 @@ SIGNATURES = {
                             ctypes.POINTER(Mask), _u32, _vp, _vp, _vp],
     "pyas_comoments_combine_segments": [_vp, _vp, _vp, _vp, _i64, _vp, _vp],
     "pyas_comoments_combine_grid": [_vp, _vp, ctypes.POINTER(Grid), _vp, _vp],
+    "pyas_trend_axes": [_vp, ctypes.POINTER(Batch), ctypes.POINTER(Mask), ctypes.POINTER(Coord), _u32, _vp, _vp,
+                        _vp],
+    "pyas_trend_cols": [_vp, ctypes.POINTER(Batch), ctypes.POINTER(Mask), ctypes.POINTER(Coord),
+                        ctypes.POINTER(Grid), _vp, _vp],
+    "pyas_trend_finalize": [_vp, _vp, _i64, _i32, _vp, _vp, _vp],
     "pyas_wsum_axes": [_vp, ctypes.POINTER(Batch), ctypes.POINTER(Mask), ctypes.POINTER(Weights), _u32, _vp, _vp,
                        _vp],
     "pyas_wsum_combine_segments": [_vp, _vp, _vp, _vp, _i64, _vp, _vp],

@@ -50,7 +50,7 @@ import warnings
 
 import numpy as np
 
-from . import _lib, comoments, engine, histogram, moments, quantile, selection, weighted, zerosign
+from . import _lib, comoments, engine, histogram, moments, quantile, selection, trend, weighted, zerosign
 from .batch import ReductionPlan, _all_full
 from .device import DeviceBuffer, get_context
 from .dtypes import native, sum_dtype
@@ -336,6 +336,8 @@ class Active:
         self._hist = None               # histogram: the bins of the next query (_check_hist)
         self._quant = None              # quantile: {"q": float64 (0-D or 1-D), "method": str} of the next query
         self._co = None                 # cov / corr: the second variable's Active of the next query
+        self._trend = None              # trend: {"along": dim >= 0, "coord": float64 vector} of the next query
+        self._trend_path = None         # the last trend query: "cols" (dense column kernel) or "walk"
         self._select_stats = None       # the last quantile query: its digit width, count launches and chains
         self._max_threads = int(max_threads)
         self.device = device
@@ -380,6 +382,15 @@ class Active:
         self._hist = None
         self._quant = None
         self._co = None
+        self._trend = None
+
+    @property
+    def trend_path(self):
+        """Which kernel the last :meth:`trend` query ran: ``"cols"`` (the dense
+        column walk, pyas_trend_cols) or ``"walk"`` (the per-element walk,
+        pyas_trend_axes); None before the first one and after a query that
+        reached no kernel (an empty selection)."""
+        return self._trend_path
 
     @property
     def weights(self):
@@ -490,6 +501,39 @@ class Active:
         masked, where either variable is constant over the counted pairs."""
         return self._set_comoments("corr", other, axis, 0)
 
+    def trend(self, along, coord=None, axis=None):
+        """The least-squares slope of the data against a coordinate, per
+        output: with ``x = coord[i]`` for an element at global index ``i``
+        along dimension ``along`` and ``y`` its value as float64,
+        ``slope = cxy / m2_x`` over the selected unmasked elements
+        (``cxy = sum (x - mean_x)(y - mean_y)``, ``m2_x = sum (x - mean_x)^2``),
+        one pass on the device.  ``along``: an int in ``[-ndim, ndim)`` that
+        must be among the reduced axes; ``coord``: 1-D, ``shape[along]`` finite
+        entries (they may repeat and need not be monotonic), ``None`` meaning
+        ``arange(shape[along])``.  The query returns a float64 masked array of
+        ``final_shape``: masked where no element counts; NaN, not masked,
+        where ``m2_x == 0`` (one counted element, or all counted coordinates
+        equal) and where a counted value is NaN or infinite; exactly 0 for
+        constant data.  With ``components`` a dict of ``slope``, ``intercept``
+        (``mean_y - slope mean_x``), ``n``, ``mean_x``, ``mean_y``, ``m2_x``,
+        ``m2_y`` and ``cxy``: the fields of a :meth:`cov` record with the
+        coordinate as ``x``, so ``comoments.merge`` combines the components of
+        disjoint selections.  A unit-step box query whose reduced axes are a
+        leading prefix of the dims (``along=0, axis=(0,)``) runs the dense
+        column kernel (pyas_trend_cols), anything else the per-element walk
+        (pyas_trend_axes): see :attr:`trend_path`.  The settings hold for one
+        query."""
+        ndim = self.ds.ndim
+        if isinstance(along, (bool, np.bool_)) or not isinstance(along, (int, np.integer)) \
+                or not -ndim <= along < ndim:
+            raise ValueError(f"trend: along={along!r} is out of range for {ndim} dimensions")
+        d = int(along) % ndim
+        self._trend = {"along": d, "coord": trend.check_coord(coord, self.ds.shape[d])}
+        self._method = "trend"
+        if axis is not None:
+            self._axis = axis
+        return self
+
     def histogram(self, bins=10, range=None, axis=None):   # noqa: A002 - NumPy's argument name
         """Binned counts of the unmasked elements, one pass on the device
         (pyas_hist_axes).  Each element converts to float64 as
@@ -584,6 +628,7 @@ class Active:
             self._hist = None            # and so are a histogram's bins
             self._quant = None           # and a quantile's q and method
             self._co = None              # and a cov / corr's second variable
+            self._trend = None           # and a trend's coordinate
             for store in held:
                 _unhold(store)
             self._held.stores = []
@@ -607,15 +652,21 @@ class Active:
         co = self._method in ("cov", "corr")
         if co and (self.group is not None or self._co.group is not None):
             raise NotImplementedError("cov/corr with group=…: co-moments are reduced on one GPU only")
+        tr = self._method == "trend"
+        if tr and self.group is not None:
+            raise NotImplementedError("trend with group=…: co-moments are reduced on one GPU only")
         if self._axis is None:
             self._axis = tuple(range(ds.ndim))
         elif isinstance(self._axis, int):
             self._axis = (self._axis,)
+        if tr and self._trend["along"] not in self._norm_axes():
+            raise ValueError(f"trend: along={self._trend['along']} is not among the reduced axes "
+                             f"{self._norm_axes()}: the coordinate would be constant per output")
         cache_key = None
-        # (var / std, weighted, histogram, quantile and cov / corr queries bypass the plan cache: its plans replay
-        # pyas_partial launches)
+        # (var / std, weighted, histogram, quantile, cov / corr and trend queries bypass the plan cache: its plans
+        # replay pyas_partial launches)
         if self.resident and self.group is None and self._method is not None and not second and not has_w \
-                and not hist and not quant and not co:
+                and not hist and not quant and not co and not tr:
             ikey = _index_key(index)
             if ikey is not None:
                 cache_key = (ikey, self._norm_axes(), _missing_key(self.missing))
@@ -643,6 +694,8 @@ class Active:
             return self._reduce_weighted(indexer, compressor, filters, self._norm_axes())
         if co:
             return self._reduce_comoments(indexer, compressor, filters, self._norm_axes())
+        if tr:
+            return self._reduce_trend(indexer, compressor, filters, self._norm_axes())
         return self._reduce(indexer, compressor, filters, self._norm_axes(), cache_key)
 
     def _norm_axes(self):
@@ -1257,6 +1310,187 @@ class Active:
         ctx.synchronize(st)
         del keep, plan, plan_y
         return fmt(final.reshape(final_shape))
+
+    # -- trend -------------------------------------------------------------------
+    def _coord_tables(self, coords):
+        """pyas_coord of this query for the chunks at ``coords``: the coordinate
+        vector zero-padded to whole chunks (so that every entry of an edge chunk
+        is readable) and each chunk's origin in it (:meth:`_weight_tables` for
+        one dim)."""
+        ds = self.ds
+        d = self._trend["along"]
+        coords = np.asarray(coords, dtype=np.int64).reshape(-1, ds.ndim)
+        padded = np.zeros(-(-ds.shape[d] // ds.chunks[d]) * ds.chunks[d], dtype=np.float64)
+        padded[:ds.shape[d]] = self._trend["coord"]
+        if padded.size >= 2 ** 31:
+            raise NotImplementedError("coordinate vectors of 2^31 entries or more")
+        return padded, (coords[:, d] * ds.chunks[d]).astype(np.int32)
+
+    def _reduce_trend(self, indexer, compressor, filters, axes):
+        """trend: co-moment records of the data against the coordinate.  A
+        unit-step box query whose reduced axes are a leading prefix of the dims
+        takes the dense column kernel (pyas_trend_cols: one finished record per
+        output, the chunk layers folded in the kernel); anything else
+        per-chunk records (pyas_trend_axes) merged in the orders of
+        :meth:`_reduce_comoments`.  The slope and its mask are computed on the
+        device (pyas_trend_finalize) unless ``components`` is set."""
+        ds = self.ds
+        along = self._trend["along"]
+        self._trend_path = None
+        final_shape = tuple(1 if i in axes else n for i, n in enumerate(indexer.shape))
+        n_final = int(np.prod(final_shape))
+        box = self._box_plan(indexer)
+        dims = None
+        if box is not None:
+            dims, coords, table, pool = box
+            n = len(coords)
+        else:
+            chunk_list = list(indexer)
+            n = len(chunk_list)
+            coords = [c for c, _ in chunk_list]
+        if n == 0 or n_final == 0:
+            return self._format_trend(np.zeros(final_shape, dtype=engine.comoments_dtype))
+        ctx, st, buf, offsets, fused = self._ingest(coords, compressor, filters)
+        if box is not None:
+            full = _all_full(table, ds.chunks)
+            sel = dict(sel_table=None if full else table, index_pool=None if full else pool)
+        else:
+            sel = dict(selections=[self._chunk_sel(projs) for _, projs in chunk_list])
+        plan = ReductionPlan(ctx, ds.dtype, ds.chunks, buf.ptr, offsets, shuffle=fused, missing=self.missing,
+                             stream=st, **sel)
+        axes_mask = 0
+        for a in axes:
+            axes_mask |= 1 << a
+        nb = _lib.COMOMENTS_NBYTES
+        fin = DeviceBuffer(ctx, n_final * nb)
+        cpool, corigin = self._coord_tables(coords)
+        cbuf = DeviceBuffer(ctx, cpool.nbytes + corigin.nbytes)
+        ctx.h2d(cbuf.ptr, cpool, st)
+        ctx.h2d(cbuf.ptr + cpool.nbytes, corigin, st)
+        keep = [buf, cbuf]
+
+        def reduce_axes(off_ptr, out_ptr):
+            engine.trend_axes(ctx, plan.batch, plan.mask_up.struct, cbuf.ptr, cbuf.ptr + cpool.nbytes, along,
+                              axes_mask, off_ptr, out_ptr, st)
+
+        def grid_struct(tables, tbuf_ptr, obuf_ptr):
+            g = _lib.Grid()
+            g.ndim = ds.ndim
+            g.axes_mask = axes_mask
+            for d in range(ds.ndim):
+                g.n_coords[d] = tables["n_coords"][d]
+                g.out_extent[d] = final_shape[d] if d not in axes else 1
+                if d not in axes and tbuf_ptr is not None:
+                    g.pos_coord[d] = tbuf_ptr + 4 * tables["pos_coord"][d]
+                    g.pos_local[d] = tbuf_ptr + 4 * tables["pos_local"][d]
+                    g.coord_count[d] = tbuf_ptr + 4 * tables["coord_count"][d]
+            g.chunk_out_offsets = obuf_ptr
+            return g
+        # the dense path: every dim one unit-step range, reduced axes 0 .. P-1, a kept dim behind them
+        dense = dims is not None and len(axes) < ds.ndim and axes == tuple(range(len(axes))) \
+            and bool(np.all(table[:, :ds.ndim, 1] == 1))
+        done = False
+        if dense:
+            g = grid_struct({"n_coords": [len(p) for p in dims]}, None, None)
+            done = engine.trend_cols(ctx, plan.batch, plan.mask_up.struct, cbuf.ptr, cbuf.ptr + cpool.nbytes, along, g,
+                                     fin.ptr, st)
+        if done:
+            self._trend_path = "cols"
+        elif len(axes) == ds.ndim:
+            # one record per chunk, folded in chunk order: groups of
+            # _COMOMENTS_SEG consecutive records per thread, level after level
+            levels, m = [], n
+            while True:
+                n_seg = -(-m // _COMOMENTS_SEG)
+                levels.append((n_seg, np.minimum(np.arange(n_seg + 1, dtype=np.int64) * _COMOMENTS_SEG, m)))
+                if n_seg == 1:
+                    break
+                m = n_seg
+            segs = np.concatenate([seg for _, seg in levels])
+            n_rec = n + sum(n_seg for n_seg, _ in levels[:-1])
+            work = DeviceBuffer(ctx, n_rec * nb + segs.nbytes)
+            keep.append(work)
+            cur, sptr = work.ptr, work.ptr + n_rec * nb
+            ctx.h2d(sptr, segs, st)
+            reduce_axes(None, cur)
+            nxt = cur + n * nb
+            for n_seg, seg in levels:
+                dst = fin.ptr if n_seg == 1 else nxt
+                engine.comoments_combine_segments(ctx, cur, None, sptr, n_seg, dst, st)
+                cur, nxt, sptr = dst, dst + n_seg * nb, sptr + seg.nbytes
+        elif dims is not None:
+            out_off, tables = self._grid_from_dims(dims, axes, final_shape)
+            obuf = DeviceBuffer(ctx, out_off.nbytes)
+            ctx.h2d(obuf.ptr, out_off, st)
+            tbuf = DeviceBuffer(ctx, max(tables["blob"].nbytes, 16))
+            ctx.h2d(tbuf.ptr, tables["blob"], st)
+            g = grid_struct(tables, tbuf.ptr, obuf.ptr)
+            parts = DeviceBuffer(ctx, max(int(tables["n_parts"]), 1) * nb)
+            reduce_axes(obuf.ptr, parts.ptr)
+            engine.comoments_combine_grid(ctx, parts.ptr, g, fin.ptr, st)
+            keep += [obuf, tbuf, parts]
+        else:
+            sizes, fidx = [], []
+            for _, projs in chunk_list:
+                pos = [p.out_pos if i not in axes else np.zeros(1, dtype=np.int64) for i, p in enumerate(projs)]
+                grids = np.meshgrid(*pos, indexing="ij")
+                fidx.append(np.ravel_multi_index([x.reshape(-1) for x in grids], final_shape))
+                sizes.append(grids[0].size)
+            out_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+            f_all = np.concatenate(fidx)
+            order = np.argsort(f_all, kind="stable").astype(np.int64)
+            seg = np.searchsorted(f_all[order], np.arange(n_final + 1)).astype(np.int64)
+            meta = np.concatenate([out_off[:-1], order, seg])
+            mbuf = DeviceBuffer(ctx, meta.nbytes)
+            ctx.h2d(mbuf.ptr, meta, st)
+            parts = DeviceBuffer(ctx, max(int(out_off[-1]), 1) * nb)
+            reduce_axes(mbuf.ptr, parts.ptr)
+            engine.comoments_combine_segments(ctx, parts.ptr, mbuf.ptr + 8 * n, mbuf.ptr + 8 * (n + order.size),
+                                              n_final, fin.ptr, st)
+            keep += [mbuf, parts]
+        if not done:
+            self._trend_path = "walk"
+        if self._components:
+            # the records, and the slope and intercept computed on the device
+            final = np.zeros(n_final, dtype=engine.comoments_dtype)
+            vbuf = DeviceBuffer(ctx, n_final * 17)
+            sl, ic = np.empty(n_final, dtype=np.float64), np.empty(n_final, dtype=np.float64)
+            engine.trend_finalize(ctx, fin.ptr, n_final, _lib.TREND_SLOPE, vbuf.ptr, vbuf.ptr + 16 * n_final, st)
+            engine.trend_finalize(ctx, fin.ptr, n_final, _lib.TREND_INTERCEPT, vbuf.ptr + 8 * n_final,
+                                  vbuf.ptr + 16 * n_final, st)
+            ctx.d2h(final, fin.ptr, st)
+            ctx.d2h(sl, vbuf.ptr, st)
+            ctx.d2h(ic, vbuf.ptr + 8 * n_final, st)
+            ctx.synchronize(st)
+            del keep, plan, vbuf
+            return self._format_trend(final.reshape(final_shape), sl.reshape(final_shape), ic.reshape(final_shape))
+        # the slope and its mask on the device: 9 bytes per output come back
+        vbuf = DeviceBuffer(ctx, n_final * 9)
+        engine.trend_finalize(ctx, fin.ptr, n_final, _lib.TREND_SLOPE, vbuf.ptr, vbuf.ptr + 8 * n_final, st)
+        val = np.empty(n_final, dtype=np.float64)
+        msk = np.empty(n_final, dtype=np.uint8)
+        ctx.d2h(val, vbuf.ptr, st)
+        ctx.d2h(msk, vbuf.ptr + 8 * n_final, st)
+        ctx.synchronize(st)
+        del keep, plan, vbuf
+        return np.ma.MaskedArray(val.reshape(final_shape), mask=msk.reshape(final_shape).astype(bool))
+
+    def _format_trend(self, parts, slope=None, intercept=None):
+        """The float64 result of a trend query from its combined records on
+        the host (trend.slope), or its components (``slope`` / ``intercept``:
+        their values as pyas_trend_finalize computed them, else computed
+        here)."""
+        if self._components:
+            empty = parts["count"] == 0
+            out = {name: np.ma.MaskedArray(np.ascontiguousarray(parts[name]), mask=empty)
+                   for name in ("mean_x", "mean_y", "m2_x", "m2_y", "cxy")}
+            out["n"] = np.ma.MaskedArray(np.ascontiguousarray(parts["count"]),
+                                         mask=np.zeros(parts.shape, dtype=bool))
+            out["slope"] = trend.slope(parts) if slope is None else np.ma.MaskedArray(slope, mask=empty)
+            out["intercept"] = trend.intercept(parts) if intercept is None else \
+                np.ma.MaskedArray(intercept, mask=empty)
+            return out
+        return trend.slope(parts)
 
     # -- histogram ------------------------------------------------------------------
     def _auto_range(self, index, compressor, filters):

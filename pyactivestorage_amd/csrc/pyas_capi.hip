@@ -1683,6 +1683,136 @@ int pyas_comoments_combine_grid(pyas_ctx *ctx, const pyas_comoments *in, const p
     return PYAS_OK;
 }
 
+// pyas_trend_axes / pyas_trend_cols: the checks of the coordinate
+static int check_coord(const pyas_coord *coord, int ndim, uint32_t axes_mask) {
+    if (!coord || !coord->pool || !coord->origin) return fail(PYAS_EINVAL, "coord is NULL or has a NULL table");
+    if (coord->dim < 0 || coord->dim >= ndim)
+        return fail(PYAS_EINVAL, "coord dim %d outside rank %d", coord->dim, ndim);
+    if (!((axes_mask >> coord->dim) & 1u))
+        return fail(PYAS_EINVAL, "coord dim %d is not among the reduced dims 0x%x", coord->dim, axes_mask);
+    return PYAS_OK;
+}
+
+int pyas_trend_axes(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask, const pyas_coord *coord,
+                    uint32_t axes_mask, const int64_t *out_offsets, pyas_comoments *out, void *stream) {
+    if (!ctx) return fail(PYAS_EINVAL, "ctx is NULL");
+    if (batch && (batch->ndim < 1 || batch->ndim > PYAS_MAX_DIMS))
+        return fail(PYAS_ENOTSUP, "chunk rank %d outside 1..%d", batch->ndim, PYAS_MAX_DIMS);
+    pyas::TrendArgs x;
+    std::memset(&x, 0, sizeof(x));
+    int es;
+    bool shuf, bsw, masked;
+    int rc = prepare(ctx, batch, mask, x.r, es, shuf, bsw, masked);
+    if (rc) return rc;
+    if (axes_mask >> batch->ndim) return fail(PYAS_EINVAL, "axes mask 0x%x beyond rank %d", axes_mask, batch->ndim);
+    rc = check_coord(coord, batch->ndim, axes_mask);
+    if (rc) return rc;
+    const int64_t n = batch->n_chunks;
+    if (n == 0) return PYAS_OK;
+    if (!out) return fail(PYAS_EINVAL, "out is NULL");
+    const bool all = axes_mask == (1u << batch->ndim) - 1u;
+    if (!all && !out_offsets) return fail(PYAS_EINVAL, "out_offsets is NULL");
+    PYAS_HIP(hipSetDevice(ctx->device));
+    x.axes = axes_mask;
+    x.out_offsets = out_offsets;
+    x.out = out;
+    x.cpool = coord->pool;
+    x.corigin = coord->origin;
+    x.cdim = coord->dim;
+    x.shuf = shuf;
+    x.bswap = bsw;
+    int64_t keep_elems = 1;
+    for (int d = 0; d < batch->ndim; ++d)
+        if (!((axes_mask >> d) & 1u)) keep_elems *= batch->chunk_shape[d];
+    x.row = ((axes_mask >> (batch->ndim - 1)) & 1u) != 0;
+    // outputs per workgroup pass, as in pyas_moments_axes (every dim reduced: one wave per chunk)
+    const int64_t per_block = x.row ? (pyas::kBlock / pyas::kWave) * 16 : pyas::kBlock;
+    int64_t bpc = (keep_elems + per_block - 1) / per_block;
+    if (bpc > 64) bpc = 64;
+    if (bpc < 1) bpc = 1;
+    x.bpc = bpc;
+    const int64_t grid = n * bpc;
+    if (grid >= (int64_t(1) << 31)) return fail(PYAS_ENOTSUP, "grid too large");
+    PYAS_HIP(pyas::launch_trend_axes(batch->dtype, x, grid, (hipStream_t)stream));
+    return PYAS_OK;
+}
+
+int pyas_trend_cols(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask, const pyas_coord *coord,
+                    const pyas_grid *g, pyas_comoments *out, void *stream) {
+    if (!ctx) return fail(PYAS_EINVAL, "ctx is NULL");
+    if (!g) return fail(PYAS_EINVAL, "grid is NULL");
+    if (batch && (batch->ndim < 1 || batch->ndim > PYAS_MAX_DIMS))
+        return fail(PYAS_ENOTSUP, "chunk rank %d outside 1..%d", batch->ndim, PYAS_MAX_DIMS);
+    pyas::TrendColsArgs x;
+    std::memset(&x, 0, sizeof(x));
+    int es;
+    bool shuf, bsw, masked;
+    int rc = prepare(ctx, batch, mask, x.r, es, shuf, bsw, masked);
+    if (rc) return rc;
+    const int nd = batch->ndim;
+    if (g->ndim != nd) return fail(PYAS_EINVAL, "grid rank %d, chunk rank %d", g->ndim, nd);
+    if (g->axes_mask >> nd) return fail(PYAS_EINVAL, "axes mask 0x%x beyond rank %d", g->axes_mask, nd);
+    rc = check_coord(coord, nd, g->axes_mask);
+    if (rc) return rc;
+    int64_t n_layers = 1, n_cols = 1, n_out = 1;
+    for (int d = 0; d < nd; ++d) {
+        if (g->n_coords[d] < 1) return fail(PYAS_EINVAL, "n_coords[%d] = %lld", d, (long long)g->n_coords[d]);
+        if ((g->axes_mask >> d) & 1u) {
+            n_layers *= g->n_coords[d];
+        } else {
+            if (g->out_extent[d] < 1) return fail(PYAS_EINVAL, "out_extent[%d] = %lld", d, (long long)g->out_extent[d]);
+            n_cols *= g->n_coords[d];
+            n_out *= g->out_extent[d];
+        }
+    }
+    if (batch->n_chunks != n_layers * n_cols)
+        return fail(PYAS_EINVAL, "%lld chunks for a grid of %lld", (long long)batch->n_chunks,
+                    (long long)(n_layers * n_cols));
+    // the geometries the column walk takes: reduced dims 0 .. P-1, at least one kept dim behind them
+    int P = 0;
+    while (P < nd && ((g->axes_mask >> P) & 1u)) ++P;
+    if (P == 0 || P == nd || g->axes_mask != (1u << P) - 1u)
+        return fail(PYAS_ENOTSUP, "reduced dims 0x%x are not a leading prefix with a kept dim behind it", g->axes_mask);
+    if (x.r.tab.on[0] || x.r.tab.on[1]) return fail(PYAS_ENOTSUP, "vector mask tables");
+    if (!out) return fail(PYAS_EINVAL, "out is NULL");
+    int64_t items = (batch->chunk_shape[nd - 1] + pyas::kTrendV - 1) / pyas::kTrendV;
+    for (int d = P; d < nd - 1; ++d) items *= batch->chunk_shape[d];
+    const int64_t bpc = (items + pyas::kBlock - 1) / pyas::kBlock;
+    const int64_t grid = n_cols * bpc;
+    if (grid >= (int64_t(1) << 31)) return fail(PYAS_ENOTSUP, "grid of %lld workgroups", (long long)grid);
+    PYAS_HIP(hipSetDevice(ctx->device));
+    x.P = P;
+    x.cdim = coord->dim;
+    x.cpool = coord->pool;
+    x.corigin = coord->origin;
+    int64_t stride = 1;
+    for (int d = nd - 1; d >= 0; --d) {
+        x.n_coords[d] = g->n_coords[d];
+        x.ostride[d] = stride;
+        if (d >= P) stride *= g->out_extent[d];
+    }
+    x.n_layers = n_layers;
+    x.n_cols = n_cols;
+    x.bpc = bpc;
+    x.out = out;
+    x.bswap = bsw;
+    x.masked = masked;
+    PYAS_HIP(pyas::launch_trend_cols(batch->dtype, x, shuf, grid, (hipStream_t)stream));
+    return PYAS_OK;
+}
+
+int pyas_trend_finalize(pyas_ctx *ctx, const pyas_comoments *in, int64_t n, int32_t what, double *value,
+                        uint8_t *masked, void *stream) {
+    if (!ctx) return fail(PYAS_EINVAL, "ctx is NULL");
+    if (n < 0) return fail(PYAS_EINVAL, "negative record count");
+    if (what != PYAS_TREND_SLOPE && what != PYAS_TREND_INTERCEPT) return fail(PYAS_EINVAL, "what = %d", what);
+    if (n == 0) return PYAS_OK;
+    if (!in || !value || !masked) return fail(PYAS_EINVAL, "NULL argument");
+    PYAS_HIP(hipSetDevice(ctx->device));
+    PYAS_HIP(pyas::launch_trend_finalize(in, n, what, value, masked, (hipStream_t)stream));
+    return PYAS_OK;
+}
+
 int pyas_wsum_axes(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask, const pyas_weights *weights,
                    uint32_t axes_mask, const int64_t *out_offsets, pyas_wsum *out, void *stream) {
     if (!ctx) return fail(PYAS_EINVAL, "ctx is NULL");

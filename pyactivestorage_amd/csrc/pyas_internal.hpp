@@ -294,6 +294,38 @@ hipError_t launch_comoments_segments(const pyas_comoments *in, const int64_t *in
                                      int64_t n_seg, pyas_comoments *out, hipStream_t st);
 hipError_t launch_comoments_grid(const pyas_comoments *in, const pyas_grid &g, int64_t n_out, int64_t n_layers,
                                  pyas_comoments *out, hipStream_t st);
+// least-squares trend against a coordinate (pyas_trend.hip): pyas_comoments records, x = the coordinate
+struct TrendArgs {
+    ReduceArgs r;                     // r.out unused
+    uint32_t axes;                    // reduced dims (cdim among them)
+    int64_t bpc;                      // workgroups per chunk
+    const int64_t *out_offsets;       // NULL (every dim reduced only): chunk c's record at out[c]
+    pyas_comoments *out;
+    const double *cpool;              // pyas_coord
+    const int32_t *corigin;
+    int32_t cdim;
+    bool shuf, bswap;
+    bool row;                         // innermost dim reduced: a wave per output
+};
+constexpr int kTrendV = 4;            // k_trend_cols: consecutive outputs per lane
+constexpr int kTrendRows = 1024;      // k_trend_cols: rows of a chunk layer staged in LDS per pass
+struct TrendColsArgs {
+    ReduceArgs r;                     // r.out unused; r.sel NULL: whole chunks
+    int32_t P;                        // dims 0 .. P-1 are reduced, P .. ndim-1 kept
+    int32_t cdim;                     // < P
+    const double *cpool;              // pyas_coord
+    const int32_t *corigin;
+    int64_t n_coords[PYAS_MAX_DIMS];  // chunk coordinates per dim (chunk n = C-order position)
+    int64_t ostride[PYAS_MAX_DIMS];   // final-output element strides (kept dims)
+    int64_t n_layers, n_cols;         // chunks along the reduced dims / kept dims
+    int64_t bpc;                      // workgroups per column
+    pyas_comoments *out;              // one finished record per final output
+    bool bswap, masked;
+};
+hipError_t launch_trend_axes(int dtype, const TrendArgs &a, int64_t grid, hipStream_t st);
+hipError_t launch_trend_cols(int dtype, const TrendColsArgs &a, bool shuf, int64_t grid, hipStream_t st);
+hipError_t launch_trend_finalize(const pyas_comoments *in, int64_t n, int32_t what, double *value, uint8_t *masked,
+                                 hipStream_t st);
 // weighted sums (pyas_weighted.hip): count / sum w / sum w x records
 struct WsumArgs {
     ReduceArgs r;                     // r.out unused

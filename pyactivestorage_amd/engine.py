@@ -262,6 +262,37 @@ def comoments_combine_grid(ctx: Context, in_ptr, grid: _lib.Grid, out_ptr, strea
                "pyas_comoments_combine_grid")
 
 
+def trend_axes(ctx: Context, batch: _lib.Batch, mask: _lib.Mask, pool_ptr, origin_ptr, dim: int, axes_mask: int,
+               out_offsets_ptr, out_ptr, stream) -> None:
+    """pyas_trend_axes: co-moment records of the data against a coordinate per
+    chunk output, laid out like :func:`moments_axes`'; ``pool_ptr`` /
+    ``origin_ptr`` / ``dim``: pyas_coord."""
+    c = _lib.Coord(pool_ptr, origin_ptr, int(dim))
+    _lib.check(ctx.lib.pyas_trend_axes(ctx.handle, ctypes.byref(batch), ctypes.byref(mask), ctypes.byref(c),
+                                       int(axes_mask), out_offsets_ptr, out_ptr, stream), "pyas_trend_axes")
+
+
+def trend_cols(ctx: Context, batch: _lib.Batch, mask: _lib.Mask, pool_ptr, origin_ptr, dim: int, grid: _lib.Grid,
+               out_ptr, stream) -> bool:
+    """pyas_trend_cols: one finished record per final output of a unit-step
+    box query, in one launch.  False (nothing launched) when the geometry is
+    not the dense path's (PYAS_ENOTSUP): the caller runs :func:`trend_axes`."""
+    c = _lib.Coord(pool_ptr, origin_ptr, int(dim))
+    rc = ctx.lib.pyas_trend_cols(ctx.handle, ctypes.byref(batch), ctypes.byref(mask), ctypes.byref(c),
+                                 ctypes.byref(grid), out_ptr, stream)
+    if rc == _lib.ENOTSUP:
+        return False
+    _lib.check(rc, "pyas_trend_cols")
+    return True
+
+
+def trend_finalize(ctx: Context, in_ptr, n: int, what: int, value_ptr, mask_ptr, stream) -> None:
+    """pyas_trend_finalize: slope (``_lib.TREND_SLOPE``) or intercept of ``n``
+    records as float64 values and mask bytes, on the device."""
+    _lib.check(ctx.lib.pyas_trend_finalize(ctx.handle, in_ptr, int(n), int(what), value_ptr, mask_ptr, stream),
+               "pyas_trend_finalize")
+
+
 def hist_axes(ctx: Context, batch: _lib.Batch, mask: _lib.Mask, edges_ptr, n_bins: int, uniform, axes_mask: int,
               out_offsets_ptr, out_index_ptr, table_ptr, stream) -> None:
     """pyas_hist_axes: binned counts added into int64 table rows of
