@@ -45,6 +45,7 @@ from __future__ import annotations
 import concurrent.futures
 import os
 import threading
+from types import SimpleNamespace
 
 import warnings
 
@@ -62,9 +63,7 @@ from .storage import _decompress, _shuffle_sizes
 from .variable import ChunkedVariable, decode_filters, get_missing_attributes
 
 _ALIGN = 256
-_MOMENTS_SEG = 64   # records a thread folds per level of a full var / std reduction
-_WSUM_SEG = 64      # the same for a full weighted mean / sum reduction
-_COMOMENTS_SEG = 64  # and for a full cov / corr reduction
+_RECORD_SEG = 64   # records a thread folds per level of a full record reduction (var, weighted, cov, trend)
 _RESIDENT_LOCK = threading.Lock()
 _RESIDENT_CV = threading.Condition(_RESIDENT_LOCK)   # slot state changes
 _EMPTY, _LOADING, _LOADED = 0, 1, 2
@@ -273,6 +272,77 @@ def _pipeline_groups(sizes, n_groups):
 # run returns the reduction with the device's sign of a zero min/max and a
 # RuntimeWarning, instead of raising (the default keeps NumPy's bytes or fails)
 _SIGN_FALLBACK_WARN = os.environ.get("PYAS_ZERO_SIGN_FALLBACK", "") == "warn"
+
+
+def _axes_mask(axes):
+    """The ABI's axes mask: bit d set for every reduced dim d."""
+    mask = 0
+    for a in axes:
+        mask |= 1 << a
+    return mask
+
+
+def _grid_struct(ndim, axes, final_shape, tables, tbuf_ptr, offsets_ptr):
+    """pyas_grid of a box query from ``_grid_from_dims``' tables, whose blob
+    lies on the device at ``tbuf_ptr``: a kept dim gets its three position
+    tables, a reduced dim extent 1 and none.  ``tbuf_ptr`` None (only
+    ``tables["n_coords"]`` is read then) leaves every table NULL, for a launch
+    that takes the chunk grid alone."""
+    g = _lib.Grid()
+    g.ndim = ndim
+    g.axes_mask = _axes_mask(axes)
+    for d in range(ndim):
+        g.n_coords[d] = tables["n_coords"][d]
+        g.out_extent[d] = final_shape[d] if d not in axes else 1
+        if d not in axes and tbuf_ptr is not None:
+            g.pos_coord[d] = tbuf_ptr + 4 * tables["pos_coord"][d]
+            g.pos_local[d] = tbuf_ptr + 4 * tables["pos_local"][d]
+            g.coord_count[d] = tbuf_ptr + 4 * tables["coord_count"][d]
+    g.chunk_out_offsets = offsets_ptr
+    return g
+
+
+def _chunk_outputs(chunk_projs, axes, final_shape):
+    """Where each chunk's partial outputs go.  ``chunk_projs``: per chunk, its
+    per-dim projections.  Returns ``(out_off, f_all)``: chunk k's outputs (C
+    order over its kept selected dims) are entries ``out_off[k]:out_off[k+1]``
+    of ``f_all``, each the flat index of its final output."""
+    sizes, fidx = [], []
+    for projs in chunk_projs:
+        pos = [np.asarray(p.out_pos, dtype=np.int64) if i not in axes else np.zeros(1, dtype=np.int64)
+               for i, p in enumerate(projs)]
+        grids = np.meshgrid(*pos, indexing="ij")
+        fidx.append(np.ravel_multi_index([x.reshape(-1) for x in grids], final_shape))
+        sizes.append(grids[0].size)
+    out_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    return out_off, np.concatenate(fidx).astype(np.int64, copy=False)
+
+
+def _segment_meta(chunk_projs, axes, final_shape):
+    """Segments of a ``*_combine_segments`` call over the partial outputs of
+    :func:`_chunk_outputs`: ``(out_off, order, seg)``, final output f
+    combining the partial outputs ``order[seg[f]:seg[f+1]]``, in chunk order
+    (a stable sort)."""
+    out_off, f_all = _chunk_outputs(chunk_projs, axes, final_shape)
+    order = np.argsort(f_all, kind="stable").astype(np.int64)
+    seg = np.searchsorted(f_all[order], np.arange(int(np.prod(final_shape)) + 1)).astype(np.int64)
+    return out_off, order, seg
+
+
+def _fold_levels(n, seg=_RECORD_SEG):
+    """The fold of ``n`` per-chunk records into one, in chunk order: groups of
+    ``seg`` consecutive records per thread, level after level (a fixed
+    function of the chunk count alone).  Returns ``(levels, n_rec)``: per
+    level its segment count and segment bounds, and the records the per-chunk
+    pass and every level but the last write."""
+    levels, m = [], n
+    while True:
+        n_seg = -(-m // seg)
+        levels.append((n_seg, np.minimum(np.arange(n_seg + 1, dtype=np.int64) * seg, m)))
+        if n_seg == 1:
+            break
+        m = n_seg
+    return levels, n + sum(n_seg for n_seg, _ in levels[:-1])
 
 
 def _sign_fallback(err):
@@ -1066,111 +1136,120 @@ class Active:
         return self._format(final.reshape(final_shape), final_shape)
 
     # -- var / std ------------------------------------------------------------
-    def _reduce_moments(self, indexer, compressor, filters, axes):
-        """var / std: per-chunk count / mean / m2 records (pyas_moments_axes)
-        merged with Chan's formula in the order the sums are combined in: a
-        full reduction in chunk order, a box query over the chunk layers of
-        each output (pyas_moments_combine_grid), anything else over host-built
-        segments (pyas_moments_combine_segments)."""
+    def _query_plan(self, indexer, compressor, filters, axes, pair=None):
+        """What a record or counting query launches over: the query's chunks on
+        the device and their plan.  A namespace of ``final_shape``, ``n_final``,
+        ``axes_mask``, ``coords`` (the chunks' coordinates in launch order),
+        ``n``, ``dims`` / ``table`` (a box query) or ``chunk_list`` (anything
+        else), and ``empty``; unless the query selects nothing, also ``ctx``,
+        ``st``, ``plan`` and ``keep`` (the buffers to hold until the stream is
+        synchronised).  ``pair`` (cov / corr): a second Active whose chunks at
+        the same coordinates are ingested too, with ``plan_y`` over them and
+        the same selections; a vector fill or missing value on either side
+        needs per-chunk selections."""
         ds = self.ds
-        final_shape = tuple(1 if i in axes else n for i, n in enumerate(indexer.shape))
-        n_final = int(np.prod(final_shape))
-        final = np.zeros(n_final, dtype=engine.moments_dtype)
-        box = self._box_plan(indexer)
-        dims = None
+        q = SimpleNamespace(dims=None, table=None, chunk_list=None, axes_mask=_axes_mask(axes))
+        q.final_shape = tuple(1 if i in axes else n for i, n in enumerate(indexer.shape))
+        q.n_final = int(np.prod(q.final_shape))
+        missing_y = get_missing_attributes(pair.ds.attrs) if pair is not None else ()
+        box = None if any(m is not None and np.size(m) != 1 for m in missing_y) else self._box_plan(indexer)
         if box is not None:
-            dims, coords, table, pool = box
-            n = len(coords)
+            q.dims, q.coords, q.table, pool = box
         else:
-            chunk_list = list(indexer)
-            n = len(chunk_list)
-        if n == 0 or n_final == 0:
-            return self._format_moments(final.reshape(final_shape))
+            q.chunk_list = list(indexer)
+            q.coords = [c for c, _ in q.chunk_list]
+        q.n = len(q.coords)
+        q.empty = q.n == 0 or q.n_final == 0
+        if q.empty:
+            return q
+        q.ctx, q.st, buf, offsets, fused = self._ingest(q.coords, compressor, filters)
+        q.keep = [buf]
+        if pair is not None and pair is not self:
+            _, yst, ybuf, yoffsets, yfused = self._ingest_other(pair, q.coords)
+            if yst != q.st:    # (one stream per thread and device: both ingests share it)
+                q.ctx.stream_wait(q.st, yst)
+            q.keep.append(ybuf)
+        elif pair is not None:
+            ybuf, yoffsets, yfused = buf, offsets, fused
         if box is not None:
-            ctx, st, buf, offsets, fused = self._ingest(coords, compressor, filters)
-            full = _all_full(table, ds.chunks)
-            plan = ReductionPlan(ctx, ds.dtype, ds.chunks, buf.ptr, offsets, shuffle=fused,
-                                 sel_table=None if full else table, index_pool=None if full else pool,
-                                 missing=self.missing, stream=st)
+            full = _all_full(q.table, ds.chunks)   # whole chunks: no table
+            sel = dict(sel_table=None if full else q.table, index_pool=None if full else pool)
         else:
-            ctx, st, buf, offsets, fused = self._ingest([c for c, _ in chunk_list], compressor, filters)
-            sels = [self._chunk_sel(projs) for _, projs in chunk_list]
-            plan = ReductionPlan(ctx, ds.dtype, ds.chunks, buf.ptr, offsets, shuffle=fused, selections=sels,
-                                 missing=self.missing, stream=st)
-        axes_mask = 0
-        for a in axes:
-            axes_mask |= 1 << a
-        nb = _lib.MOMENTS_NBYTES
-        fin = DeviceBuffer(ctx, n_final * nb)
-        keep = [buf]
-        if len(axes) == ds.ndim:
-            # one record per chunk, folded in chunk order: groups of _MOMENTS_SEG
-            # consecutive records per thread, level after level (a fixed
-            # function of the chunk count alone)
-            # (one allocation: every level's records, then every level's segment bounds)
-            levels, m = [], n
-            while True:
-                n_seg = -(-m // _MOMENTS_SEG)
-                levels.append((n_seg, np.minimum(np.arange(n_seg + 1, dtype=np.int64) * _MOMENTS_SEG, m)))
-                if n_seg == 1:
-                    break
-                m = n_seg
+            sel = dict(selections=[self._chunk_sel(projs) for _, projs in q.chunk_list])
+        q.plan = ReductionPlan(q.ctx, ds.dtype, ds.chunks, buf.ptr, offsets, shuffle=fused, missing=self.missing,
+                               stream=q.st, **sel)
+        if pair is not None:
+            q.plan_y = ReductionPlan(q.ctx, pair.ds.dtype, pair.ds.chunks, ybuf.ptr, yoffsets, shuffle=yfused,
+                                     missing=missing_y, stream=q.st, **sel)
+        return q
+
+    def _reduce_records(self, q, axes, nb, launch, combine_segments, combine_grid, fin=None):
+        """The per-chunk pass of a record query (``launch(out_offsets_ptr,
+        out_ptr)``, records of ``nb`` bytes) and the merge of its records, in
+        the order the sums are combined in: a full reduction in chunk order
+        (:func:`_fold_levels`), a box query over the chunk layers of each
+        output (``combine_grid``), anything else over host-built segments
+        (``combine_segments``).  Returns the device buffer of the ``n_final``
+        combined records and the buffers to hold until the stream is
+        synchronised."""
+        ctx, st, n = q.ctx, q.st, q.n
+        ndim = self.ds.ndim
+        if fin is None:
+            fin = DeviceBuffer(ctx, q.n_final * nb)
+        if len(axes) == ndim:
+            # one allocation: every level's records, then every level's segment bounds
+            levels, n_rec = _fold_levels(n)
             segs = np.concatenate([seg for _, seg in levels])
-            n_rec = n + sum(n_seg for n_seg, _ in levels[:-1])
             work = DeviceBuffer(ctx, n_rec * nb + segs.nbytes)
-            keep.append(work)
             cur, sptr = work.ptr, work.ptr + n_rec * nb
             ctx.h2d(sptr, segs, st)
-            engine.moments_axes(ctx, plan.batch, plan.mask_up.struct, axes_mask, None, cur, st)
+            launch(None, cur)
             nxt = cur + n * nb
             for n_seg, seg in levels:
                 dst = fin.ptr if n_seg == 1 else nxt
-                engine.moments_combine_segments(ctx, cur, None, sptr, n_seg, dst, st)
+                combine_segments(ctx, cur, None, sptr, n_seg, dst, st)
                 cur, nxt, sptr = dst, dst + n_seg * nb, sptr + seg.nbytes
-        elif dims is not None:
-            out_off, tables = self._grid_from_dims(dims, axes, final_shape)
+            return fin, [work]
+        if q.dims is not None:
+            out_off, tables = self._grid_from_dims(q.dims, axes, q.final_shape)
             obuf = DeviceBuffer(ctx, out_off.nbytes)
             ctx.h2d(obuf.ptr, out_off, st)
             tbuf = DeviceBuffer(ctx, max(tables["blob"].nbytes, 16))
             ctx.h2d(tbuf.ptr, tables["blob"], st)
-            g = _lib.Grid()
-            g.ndim = ds.ndim
-            g.axes_mask = axes_mask
-            for d in range(ds.ndim):
-                g.n_coords[d] = tables["n_coords"][d]
-                g.out_extent[d] = final_shape[d] if d not in axes else 1
-                if d not in axes:
-                    g.pos_coord[d] = tbuf.ptr + 4 * tables["pos_coord"][d]
-                    g.pos_local[d] = tbuf.ptr + 4 * tables["pos_local"][d]
-                    g.coord_count[d] = tbuf.ptr + 4 * tables["coord_count"][d]
-            g.chunk_out_offsets = obuf.ptr
+            g = _grid_struct(ndim, axes, q.final_shape, tables, tbuf.ptr, obuf.ptr)
             parts = DeviceBuffer(ctx, max(int(tables["n_parts"]), 1) * nb)
-            engine.moments_axes(ctx, plan.batch, plan.mask_up.struct, axes_mask, obuf.ptr, parts.ptr, st)
-            engine.moments_combine_grid(ctx, parts.ptr, g, fin.ptr, st)
-            keep += [obuf, tbuf, parts]
-        else:
-            sizes, fidx = [], []
-            for _, projs in chunk_list:
-                pos = [p.out_pos if i not in axes else np.zeros(1, dtype=np.int64) for i, p in enumerate(projs)]
-                grids = np.meshgrid(*pos, indexing="ij")
-                fidx.append(np.ravel_multi_index([x.reshape(-1) for x in grids], final_shape))
-                sizes.append(grids[0].size)
-            out_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-            f_all = np.concatenate(fidx)
-            order = np.argsort(f_all, kind="stable").astype(np.int64)
-            seg = np.searchsorted(f_all[order], np.arange(n_final + 1)).astype(np.int64)
-            meta = np.concatenate([out_off[:-1], order, seg])
-            mbuf = DeviceBuffer(ctx, meta.nbytes)
-            ctx.h2d(mbuf.ptr, meta, st)
-            parts = DeviceBuffer(ctx, max(int(out_off[-1]), 1) * nb)
-            engine.moments_axes(ctx, plan.batch, plan.mask_up.struct, axes_mask, mbuf.ptr, parts.ptr, st)
-            engine.moments_combine_segments(ctx, parts.ptr, mbuf.ptr + 8 * n, mbuf.ptr + 8 * (n + order.size),
-                                            n_final, fin.ptr, st)
-            keep += [mbuf, parts]
-        ctx.d2h(final, fin.ptr, st)
-        ctx.synchronize(st)
-        del keep
-        return self._format_moments(final.reshape(final_shape))
+            launch(obuf.ptr, parts.ptr)
+            combine_grid(ctx, parts.ptr, g, fin.ptr, st)
+            return fin, [obuf, tbuf, parts]
+        out_off, order, seg = _segment_meta((projs for _, projs in q.chunk_list), axes, q.final_shape)
+        meta = np.concatenate([out_off[:-1], order, seg])
+        mbuf = DeviceBuffer(ctx, meta.nbytes)
+        ctx.h2d(mbuf.ptr, meta, st)
+        parts = DeviceBuffer(ctx, max(int(out_off[-1]), 1) * nb)
+        launch(mbuf.ptr, parts.ptr)
+        combine_segments(ctx, parts.ptr, mbuf.ptr + 8 * n, mbuf.ptr + 8 * (n + order.size), q.n_final, fin.ptr, st)
+        return fin, [mbuf, parts]
+
+    def _records_back(self, q, fin, keep, dtype):
+        """The combined records of a record query on the host; ``keep`` (the
+        buffers its launches use) lives until the stream is synchronised."""
+        final = np.zeros(q.n_final, dtype=dtype)
+        q.ctx.d2h(final, fin.ptr, q.st)
+        q.ctx.synchronize(q.st)
+        return final.reshape(q.final_shape)
+
+    def _reduce_moments(self, indexer, compressor, filters, axes):
+        """var / std: per-chunk count / mean / m2 records (pyas_moments_axes)
+        merged with Chan's formula in the orders of :meth:`_reduce_records`."""
+        q = self._query_plan(indexer, compressor, filters, axes)
+        if q.empty:
+            return self._format_moments(np.zeros(q.final_shape, dtype=engine.moments_dtype))
+
+        def launch(off_ptr, out_ptr):
+            engine.moments_axes(q.ctx, q.plan.batch, q.plan.mask_up.struct, q.axes_mask, off_ptr, out_ptr, q.st)
+        fin, keep = self._reduce_records(q, axes, _lib.MOMENTS_NBYTES, launch, engine.moments_combine_segments,
+                                         engine.moments_combine_grid)
+        return self._format_moments(self._records_back(q, fin, keep, engine.moments_dtype))
 
     # -- cov / corr -----------------------------------------------------------
     def _ingest_other(self, other, coords):
@@ -1193,123 +1272,18 @@ class Active:
     def _reduce_comoments(self, indexer, compressor, filters, axes):
         """cov / corr: per-chunk count / means / m2s / cxy records of the two
         variables' pairs (pyas_comoments_axes: one plan per side, over the same
-        chunk list and selections) merged in the order :meth:`_reduce_moments`
-        merges its records in: a full reduction in chunk order, a box query
-        over the chunk layers of each output (pyas_comoments_combine_grid),
-        anything else over host-built segments
-        (pyas_comoments_combine_segments)."""
-        ds, other = self.ds, self._co
-        yds = other.ds
-        missing_y = get_missing_attributes(yds.attrs)
-        final_shape = tuple(1 if i in axes else n for i, n in enumerate(indexer.shape))
-        n_final = int(np.prod(final_shape))
-        final = np.zeros(n_final, dtype=engine.comoments_dtype)
-        fmt = self._format_comoments
-        # (vector fill/missing values on either side need per-chunk selections)
-        box = None if any(m is not None and np.size(m) != 1 for m in missing_y) else self._box_plan(indexer)
-        dims = None
-        if box is not None:
-            dims, coords, table, pool = box
-            n = len(coords)
-        else:
-            chunk_list = list(indexer)
-            n = len(chunk_list)
-            coords = [c for c, _ in chunk_list]
-        if n == 0 or n_final == 0:
-            return fmt(final.reshape(final_shape))
-        ctx, st, buf, offsets, fused = self._ingest(coords, compressor, filters)
-        if other is self:
-            ybuf, yoffsets, yfused = buf, offsets, fused
-        else:
-            _, yst, ybuf, yoffsets, yfused = self._ingest_other(other, coords)
-            if yst != st:    # (one stream per thread and device: both ingests share it)
-                ctx.stream_wait(st, yst)
-        if box is not None:
-            full = _all_full(table, ds.chunks)
-            sel = dict(sel_table=None if full else table, index_pool=None if full else pool)
-        else:
-            sel = dict(selections=[self._chunk_sel(projs) for _, projs in chunk_list])
-        plan = ReductionPlan(ctx, ds.dtype, ds.chunks, buf.ptr, offsets, shuffle=fused, missing=self.missing,
-                             stream=st, **sel)
-        plan_y = ReductionPlan(ctx, yds.dtype, yds.chunks, ybuf.ptr, yoffsets, shuffle=yfused, missing=missing_y,
-                               stream=st, **sel)
-        axes_mask = 0
-        for a in axes:
-            axes_mask |= 1 << a
-        nb = _lib.COMOMENTS_NBYTES
-        fin = DeviceBuffer(ctx, n_final * nb)
-        keep = [buf, ybuf]
+        chunk list and selections) merged in the orders of
+        :meth:`_reduce_records`."""
+        q = self._query_plan(indexer, compressor, filters, axes, pair=self._co)
+        if q.empty:
+            return self._format_comoments(np.zeros(q.final_shape, dtype=engine.comoments_dtype))
 
-        def reduce_axes(off_ptr, out_ptr):
-            engine.comoments_axes(ctx, plan.batch, plan.mask_up.struct, plan_y.batch, plan_y.mask_up.struct,
-                                  axes_mask, off_ptr, out_ptr, st)
-        if len(axes) == ds.ndim:
-            # one record per chunk, folded in chunk order: groups of
-            # _COMOMENTS_SEG consecutive records per thread, level after level
-            # (one allocation: every level's records, then every level's segment bounds)
-            levels, m = [], n
-            while True:
-                n_seg = -(-m // _COMOMENTS_SEG)
-                levels.append((n_seg, np.minimum(np.arange(n_seg + 1, dtype=np.int64) * _COMOMENTS_SEG, m)))
-                if n_seg == 1:
-                    break
-                m = n_seg
-            segs = np.concatenate([seg for _, seg in levels])
-            n_rec = n + sum(n_seg for n_seg, _ in levels[:-1])
-            work = DeviceBuffer(ctx, n_rec * nb + segs.nbytes)
-            keep.append(work)
-            cur, sptr = work.ptr, work.ptr + n_rec * nb
-            ctx.h2d(sptr, segs, st)
-            reduce_axes(None, cur)
-            nxt = cur + n * nb
-            for n_seg, seg in levels:
-                dst = fin.ptr if n_seg == 1 else nxt
-                engine.comoments_combine_segments(ctx, cur, None, sptr, n_seg, dst, st)
-                cur, nxt, sptr = dst, dst + n_seg * nb, sptr + seg.nbytes
-        elif dims is not None:
-            out_off, tables = self._grid_from_dims(dims, axes, final_shape)
-            obuf = DeviceBuffer(ctx, out_off.nbytes)
-            ctx.h2d(obuf.ptr, out_off, st)
-            tbuf = DeviceBuffer(ctx, max(tables["blob"].nbytes, 16))
-            ctx.h2d(tbuf.ptr, tables["blob"], st)
-            g = _lib.Grid()
-            g.ndim = ds.ndim
-            g.axes_mask = axes_mask
-            for d in range(ds.ndim):
-                g.n_coords[d] = tables["n_coords"][d]
-                g.out_extent[d] = final_shape[d] if d not in axes else 1
-                if d not in axes:
-                    g.pos_coord[d] = tbuf.ptr + 4 * tables["pos_coord"][d]
-                    g.pos_local[d] = tbuf.ptr + 4 * tables["pos_local"][d]
-                    g.coord_count[d] = tbuf.ptr + 4 * tables["coord_count"][d]
-            g.chunk_out_offsets = obuf.ptr
-            parts = DeviceBuffer(ctx, max(int(tables["n_parts"]), 1) * nb)
-            reduce_axes(obuf.ptr, parts.ptr)
-            engine.comoments_combine_grid(ctx, parts.ptr, g, fin.ptr, st)
-            keep += [obuf, tbuf, parts]
-        else:
-            sizes, fidx = [], []
-            for _, projs in chunk_list:
-                pos = [p.out_pos if i not in axes else np.zeros(1, dtype=np.int64) for i, p in enumerate(projs)]
-                grids = np.meshgrid(*pos, indexing="ij")
-                fidx.append(np.ravel_multi_index([x.reshape(-1) for x in grids], final_shape))
-                sizes.append(grids[0].size)
-            out_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-            f_all = np.concatenate(fidx)
-            order = np.argsort(f_all, kind="stable").astype(np.int64)
-            seg = np.searchsorted(f_all[order], np.arange(n_final + 1)).astype(np.int64)
-            meta = np.concatenate([out_off[:-1], order, seg])
-            mbuf = DeviceBuffer(ctx, meta.nbytes)
-            ctx.h2d(mbuf.ptr, meta, st)
-            parts = DeviceBuffer(ctx, max(int(out_off[-1]), 1) * nb)
-            reduce_axes(mbuf.ptr, parts.ptr)
-            engine.comoments_combine_segments(ctx, parts.ptr, mbuf.ptr + 8 * n, mbuf.ptr + 8 * (n + order.size),
-                                              n_final, fin.ptr, st)
-            keep += [mbuf, parts]
-        ctx.d2h(final, fin.ptr, st)
-        ctx.synchronize(st)
-        del keep, plan, plan_y
-        return fmt(final.reshape(final_shape))
+        def launch(off_ptr, out_ptr):
+            engine.comoments_axes(q.ctx, q.plan.batch, q.plan.mask_up.struct, q.plan_y.batch, q.plan_y.mask_up.struct,
+                                  q.axes_mask, off_ptr, out_ptr, q.st)
+        fin, keep = self._reduce_records(q, axes, _lib.COMOMENTS_NBYTES, launch, engine.comoments_combine_segments,
+                                         engine.comoments_combine_grid)
+        return self._format_comoments(self._records_back(q, fin, keep, engine.comoments_dtype))
 
     # -- trend -------------------------------------------------------------------
     def _coord_tables(self, coords):
@@ -1332,137 +1306,51 @@ class Active:
         takes the dense column kernel (pyas_trend_cols: one finished record per
         output, the chunk layers folded in the kernel); anything else
         per-chunk records (pyas_trend_axes) merged in the orders of
-        :meth:`_reduce_comoments`.  The slope and its mask are computed on the
+        :meth:`_reduce_records`.  The slope and its mask are computed on the
         device (pyas_trend_finalize) unless ``components`` is set."""
         ds = self.ds
         along = self._trend["along"]
         self._trend_path = None
-        final_shape = tuple(1 if i in axes else n for i, n in enumerate(indexer.shape))
-        n_final = int(np.prod(final_shape))
-        box = self._box_plan(indexer)
-        dims = None
-        if box is not None:
-            dims, coords, table, pool = box
-            n = len(coords)
-        else:
-            chunk_list = list(indexer)
-            n = len(chunk_list)
-            coords = [c for c, _ in chunk_list]
-        if n == 0 or n_final == 0:
+        q = self._query_plan(indexer, compressor, filters, axes)
+        final_shape, n_final = q.final_shape, q.n_final
+        if q.empty:
             return self._format_trend(np.zeros(final_shape, dtype=engine.comoments_dtype))
-        ctx, st, buf, offsets, fused = self._ingest(coords, compressor, filters)
-        if box is not None:
-            full = _all_full(table, ds.chunks)
-            sel = dict(sel_table=None if full else table, index_pool=None if full else pool)
-        else:
-            sel = dict(selections=[self._chunk_sel(projs) for _, projs in chunk_list])
-        plan = ReductionPlan(ctx, ds.dtype, ds.chunks, buf.ptr, offsets, shuffle=fused, missing=self.missing,
-                             stream=st, **sel)
-        axes_mask = 0
-        for a in axes:
-            axes_mask |= 1 << a
-        nb = _lib.COMOMENTS_NBYTES
-        fin = DeviceBuffer(ctx, n_final * nb)
-        cpool, corigin = self._coord_tables(coords)
+        ctx, st, plan = q.ctx, q.st, q.plan
+        fin = DeviceBuffer(ctx, n_final * _lib.COMOMENTS_NBYTES)
+        cpool, corigin = self._coord_tables(q.coords)
         cbuf = DeviceBuffer(ctx, cpool.nbytes + corigin.nbytes)
         ctx.h2d(cbuf.ptr, cpool, st)
         ctx.h2d(cbuf.ptr + cpool.nbytes, corigin, st)
-        keep = [buf, cbuf]
 
-        def reduce_axes(off_ptr, out_ptr):
+        def launch(off_ptr, out_ptr):
             engine.trend_axes(ctx, plan.batch, plan.mask_up.struct, cbuf.ptr, cbuf.ptr + cpool.nbytes, along,
-                              axes_mask, off_ptr, out_ptr, st)
-
-        def grid_struct(tables, tbuf_ptr, obuf_ptr):
-            g = _lib.Grid()
-            g.ndim = ds.ndim
-            g.axes_mask = axes_mask
-            for d in range(ds.ndim):
-                g.n_coords[d] = tables["n_coords"][d]
-                g.out_extent[d] = final_shape[d] if d not in axes else 1
-                if d not in axes and tbuf_ptr is not None:
-                    g.pos_coord[d] = tbuf_ptr + 4 * tables["pos_coord"][d]
-                    g.pos_local[d] = tbuf_ptr + 4 * tables["pos_local"][d]
-                    g.coord_count[d] = tbuf_ptr + 4 * tables["coord_count"][d]
-            g.chunk_out_offsets = obuf_ptr
-            return g
+                              q.axes_mask, off_ptr, out_ptr, st)
         # the dense path: every dim one unit-step range, reduced axes 0 .. P-1, a kept dim behind them
-        dense = dims is not None and len(axes) < ds.ndim and axes == tuple(range(len(axes))) \
-            and bool(np.all(table[:, :ds.ndim, 1] == 1))
+        dense = q.dims is not None and len(axes) < ds.ndim and axes == tuple(range(len(axes))) \
+            and bool(np.all(q.table[:, :ds.ndim, 1] == 1))
         done = False
         if dense:
-            g = grid_struct({"n_coords": [len(p) for p in dims]}, None, None)
+            g = _grid_struct(ds.ndim, axes, final_shape, {"n_coords": [len(p) for p in q.dims]}, None, None)
             done = engine.trend_cols(ctx, plan.batch, plan.mask_up.struct, cbuf.ptr, cbuf.ptr + cpool.nbytes, along, g,
                                      fin.ptr, st)
-        if done:
-            self._trend_path = "cols"
-        elif len(axes) == ds.ndim:
-            # one record per chunk, folded in chunk order: groups of
-            # _COMOMENTS_SEG consecutive records per thread, level after level
-            levels, m = [], n
-            while True:
-                n_seg = -(-m // _COMOMENTS_SEG)
-                levels.append((n_seg, np.minimum(np.arange(n_seg + 1, dtype=np.int64) * _COMOMENTS_SEG, m)))
-                if n_seg == 1:
-                    break
-                m = n_seg
-            segs = np.concatenate([seg for _, seg in levels])
-            n_rec = n + sum(n_seg for n_seg, _ in levels[:-1])
-            work = DeviceBuffer(ctx, n_rec * nb + segs.nbytes)
-            keep.append(work)
-            cur, sptr = work.ptr, work.ptr + n_rec * nb
-            ctx.h2d(sptr, segs, st)
-            reduce_axes(None, cur)
-            nxt = cur + n * nb
-            for n_seg, seg in levels:
-                dst = fin.ptr if n_seg == 1 else nxt
-                engine.comoments_combine_segments(ctx, cur, None, sptr, n_seg, dst, st)
-                cur, nxt, sptr = dst, dst + n_seg * nb, sptr + seg.nbytes
-        elif dims is not None:
-            out_off, tables = self._grid_from_dims(dims, axes, final_shape)
-            obuf = DeviceBuffer(ctx, out_off.nbytes)
-            ctx.h2d(obuf.ptr, out_off, st)
-            tbuf = DeviceBuffer(ctx, max(tables["blob"].nbytes, 16))
-            ctx.h2d(tbuf.ptr, tables["blob"], st)
-            g = grid_struct(tables, tbuf.ptr, obuf.ptr)
-            parts = DeviceBuffer(ctx, max(int(tables["n_parts"]), 1) * nb)
-            reduce_axes(obuf.ptr, parts.ptr)
-            engine.comoments_combine_grid(ctx, parts.ptr, g, fin.ptr, st)
-            keep += [obuf, tbuf, parts]
-        else:
-            sizes, fidx = [], []
-            for _, projs in chunk_list:
-                pos = [p.out_pos if i not in axes else np.zeros(1, dtype=np.int64) for i, p in enumerate(projs)]
-                grids = np.meshgrid(*pos, indexing="ij")
-                fidx.append(np.ravel_multi_index([x.reshape(-1) for x in grids], final_shape))
-                sizes.append(grids[0].size)
-            out_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-            f_all = np.concatenate(fidx)
-            order = np.argsort(f_all, kind="stable").astype(np.int64)
-            seg = np.searchsorted(f_all[order], np.arange(n_final + 1)).astype(np.int64)
-            meta = np.concatenate([out_off[:-1], order, seg])
-            mbuf = DeviceBuffer(ctx, meta.nbytes)
-            ctx.h2d(mbuf.ptr, meta, st)
-            parts = DeviceBuffer(ctx, max(int(out_off[-1]), 1) * nb)
-            reduce_axes(mbuf.ptr, parts.ptr)
-            engine.comoments_combine_segments(ctx, parts.ptr, mbuf.ptr + 8 * n, mbuf.ptr + 8 * (n + order.size),
-                                              n_final, fin.ptr, st)
-            keep += [mbuf, parts]
+        keep = []
         if not done:
-            self._trend_path = "walk"
+            fin, keep = self._reduce_records(q, axes, _lib.COMOMENTS_NBYTES, launch,
+                                             engine.comoments_combine_segments, engine.comoments_combine_grid, fin=fin)
+        self._trend_path = "cols" if done else "walk"
         if self._components:
             # the records, and the slope and intercept computed on the device
-            final = np.zeros(n_final, dtype=engine.comoments_dtype)
             vbuf = DeviceBuffer(ctx, n_final * 17)
             sl, ic = np.empty(n_final, dtype=np.float64), np.empty(n_final, dtype=np.float64)
             engine.trend_finalize(ctx, fin.ptr, n_final, _lib.TREND_SLOPE, vbuf.ptr, vbuf.ptr + 16 * n_final, st)
             engine.trend_finalize(ctx, fin.ptr, n_final, _lib.TREND_INTERCEPT, vbuf.ptr + 8 * n_final,
                                   vbuf.ptr + 16 * n_final, st)
+            final = np.zeros(n_final, dtype=engine.comoments_dtype)
             ctx.d2h(final, fin.ptr, st)
             ctx.d2h(sl, vbuf.ptr, st)
             ctx.d2h(ic, vbuf.ptr + 8 * n_final, st)
             ctx.synchronize(st)
-            del keep, plan, vbuf
+            del keep
             return self._format_trend(final.reshape(final_shape), sl.reshape(final_shape), ic.reshape(final_shape))
         # the slope and its mask on the device: 9 bytes per output come back
         vbuf = DeviceBuffer(ctx, n_final * 9)
@@ -1472,7 +1360,7 @@ class Active:
         ctx.d2h(val, vbuf.ptr, st)
         ctx.d2h(msk, vbuf.ptr + 8 * n_final, st)
         ctx.synchronize(st)
-        del keep, plan, vbuf
+        del keep
         return np.ma.MaskedArray(val.reshape(final_shape), mask=msk.reshape(final_shape).astype(bool))
 
     def _format_trend(self, parts, slope=None, intercept=None):
@@ -1545,7 +1433,7 @@ class Active:
         if e is None:
             e = histogram.edges(n_bins, self._auto_range(index, compressor, filters))
         tab = np.zeros((n_final, slots), dtype=np.int64)
-        cp = self._count_plan(indexer, compressor, filters, axes, final_shape)
+        cp = self._count_plan(indexer, compressor, filters, axes)
         if cp is None:
             return self._format_hist(tab.reshape(final_shape + (slots,)), e)
         ctx, st, plan, axes_mask, off_ptr, idx_ptr, keep = cp
@@ -1562,60 +1450,31 @@ class Active:
         del keep
         return self._format_hist(tab.reshape(final_shape + (slots,)), e)
 
-    def _count_plan(self, indexer, compressor, filters, axes, final_shape):
+    def _count_plan(self, indexer, compressor, filters, axes):
         """What a counting query (histogram, quantile) launches over: the
-        query's chunks on the device, their plan and the map from each
-        chunk-local output to its table row.  ``(ctx, stream, plan, axes_mask,
-        out_offsets_ptr, out_index_ptr, keep)``, the two pointers None for a
-        full reduction (one row), ``keep`` the buffers to hold until the stream
-        is synchronised; None when the query selects nothing."""
+        query's chunks on the device, their plan (:meth:`_query_plan`) and the
+        map from each chunk-local output to its table row.  ``(ctx, stream,
+        plan, axes_mask, out_offsets_ptr, out_index_ptr, keep)``, the two
+        pointers None for a full reduction (one row), ``keep`` the buffers to
+        hold until the stream is synchronised; None when the query selects
+        nothing."""
         ds = self.ds
-        n_final = int(np.prod(final_shape))
-        box = self._box_plan(indexer)
-        if box is not None:
-            dims, coords, table, pool = box
-            n = len(coords)
-        else:
-            chunk_list = list(indexer)
-            n = len(chunk_list)
-        if n == 0 or n_final == 0:
+        q = self._query_plan(indexer, compressor, filters, axes)
+        if q.empty:
             return None
-        if box is not None:
-            ctx, st, buf, offsets, fused = self._ingest(coords, compressor, filters)
-            full = _all_full(table, ds.chunks)
-            plan = ReductionPlan(ctx, ds.dtype, ds.chunks, buf.ptr, offsets, shuffle=fused,
-                                 sel_table=None if full else table, index_pool=None if full else pool,
-                                 missing=self.missing, stream=st)
-        else:
-            ctx, st, buf, offsets, fused = self._ingest([c for c, _ in chunk_list], compressor, filters)
-            sels = [self._chunk_sel(projs) for _, projs in chunk_list]
-            plan = ReductionPlan(ctx, ds.dtype, ds.chunks, buf.ptr, offsets, shuffle=fused, selections=sels,
-                                 missing=self.missing, stream=st)
-        axes_mask = 0
-        for a in axes:
-            axes_mask |= 1 << a
-        keep = [buf]
         if len(axes) == ds.ndim:
-            return ctx, st, plan, axes_mask, None, None, keep
+            return q.ctx, q.st, q.plan, q.axes_mask, None, None, q.keep
         # chunk-local output (C order over the kept selected dims) -> final output
-        if box is not None:
-            idx = np.indices([len(p) for p in dims]).reshape(ds.ndim, n)
-            all_projs = ([dims[d][idx[d][k]] for d in range(ds.ndim)] for k in range(n))
+        if q.dims is not None:
+            idx = np.indices([len(p) for p in q.dims]).reshape(ds.ndim, q.n)
+            all_projs = ([q.dims[d][idx[d][k]] for d in range(ds.ndim)] for k in range(q.n))
         else:
-            all_projs = (projs for _, projs in chunk_list)
-        sizes, fidx = [], []
-        for projs in all_projs:
-            pos = [np.asarray(p.out_pos, dtype=np.int64) if i not in axes else np.zeros(1, dtype=np.int64)
-                   for i, p in enumerate(projs)]
-            grids = np.meshgrid(*pos, indexing="ij")
-            fidx.append(np.ravel_multi_index([x.reshape(-1) for x in grids], final_shape))
-            sizes.append(grids[0].size)
-        out_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-        meta = np.concatenate([out_off[:-1]] + fidx).astype(np.int64)
-        mbuf = DeviceBuffer(ctx, meta.nbytes)
-        ctx.h2d(mbuf.ptr, meta, st)
-        keep.append(mbuf)
-        return ctx, st, plan, axes_mask, mbuf.ptr, mbuf.ptr + 8 * n, keep
+            all_projs = (projs for _, projs in q.chunk_list)
+        out_off, f_all = _chunk_outputs(all_projs, axes, q.final_shape)
+        meta = np.concatenate([out_off[:-1], f_all])
+        mbuf = DeviceBuffer(q.ctx, meta.nbytes)
+        q.ctx.h2d(mbuf.ptr, meta, q.st)
+        return q.ctx, q.st, q.plan, q.axes_mask, mbuf.ptr, mbuf.ptr + 8 * q.n, q.keep + [mbuf]
 
     def _format_hist(self, tab, e):
         """The int64 counts of a histogram query from its table rows (counts,
@@ -1652,7 +1511,7 @@ class Active:
         passes = quantile.digits(width, bits)
         tot = np.zeros((n_final, 2), dtype=np.int64)
         self._select_stats = {"bits": bits, "passes": 0, "chains": 0}
-        cp = self._count_plan(indexer, compressor, filters, axes, final_shape)
+        cp = self._count_plan(indexer, compressor, filters, axes)
         if cp is None:
             return self._format_select(tot, None, final_shape)
         ctx, st, plan, axes_mask, off_ptr, idx_ptr, keep = cp
@@ -1742,118 +1601,22 @@ class Active:
 
     def _reduce_weighted(self, indexer, compressor, filters, axes):
         """mean / sum with weights: per-chunk count / sum w / sum w x records
-        (pyas_wsum_axes) added up in the order :meth:`_reduce_moments` merges
-        its records in: a full reduction in chunk order, a box query over the
-        chunk layers of each output (pyas_wsum_combine_grid), anything else
-        over host-built segments (pyas_wsum_combine_segments)."""
-        ds = self.ds
-        final_shape = tuple(1 if i in axes else n for i, n in enumerate(indexer.shape))
-        n_final = int(np.prod(final_shape))
-        final = np.zeros(n_final, dtype=engine.wsum_dtype)
-        fmt = self._format_weighted
-        box = self._box_plan(indexer)
-        dims = None
-        if box is not None:
-            dims, coords, table, pool = box
-            n = len(coords)
-        else:
-            chunk_list = list(indexer)
-            n = len(chunk_list)
-        if n == 0 or n_final == 0:
-            return fmt(final.reshape(final_shape))
-        if box is not None:
-            ctx, st, buf, offsets, fused = self._ingest(coords, compressor, filters)
-            full = _all_full(table, ds.chunks)
-            plan = ReductionPlan(ctx, ds.dtype, ds.chunks, buf.ptr, offsets, shuffle=fused,
-                                 sel_table=None if full else table, index_pool=None if full else pool,
-                                 missing=self.missing, stream=st)
-        else:
-            ctx, st, buf, offsets, fused = self._ingest([c for c, _ in chunk_list], compressor, filters)
-            sels = [self._chunk_sel(projs) for _, projs in chunk_list]
-            plan = ReductionPlan(ctx, ds.dtype, ds.chunks, buf.ptr, offsets, shuffle=fused, selections=sels,
-                                 missing=self.missing, stream=st)
-        axes_mask = 0
-        for a in axes:
-            axes_mask |= 1 << a
-        nb = _lib.WSUM_NBYTES
-        fin = DeviceBuffer(ctx, n_final * nb)
-        wpool, worigin = self._weight_tables(coords if box is not None else [c for c, _ in chunk_list])
+        (pyas_wsum_axes) added up in the orders of :meth:`_reduce_records`."""
+        q = self._query_plan(indexer, compressor, filters, axes)
+        if q.empty:
+            return self._format_weighted(np.zeros(q.final_shape, dtype=engine.wsum_dtype))
+        ctx, st = q.ctx, q.st
+        wpool, worigin = self._weight_tables(q.coords)
         wbuf = DeviceBuffer(ctx, wpool.nbytes + worigin.nbytes)
         ctx.h2d(wbuf.ptr, wpool, st)
         ctx.h2d(wbuf.ptr + wpool.nbytes, worigin, st)
-        keep = [buf, wbuf]
 
-        def reduce_axes(off_ptr, out_ptr, st):
-            engine.wsum_axes(ctx, plan.batch, plan.mask_up.struct, wbuf.ptr, wbuf.ptr + wpool.nbytes, axes_mask,
+        def launch(off_ptr, out_ptr):
+            engine.wsum_axes(ctx, q.plan.batch, q.plan.mask_up.struct, wbuf.ptr, wbuf.ptr + wpool.nbytes, q.axes_mask,
                              off_ptr, out_ptr, st)
-        if len(axes) == ds.ndim:
-            # one record per chunk, folded in chunk order: groups of _WSUM_SEG
-            # consecutive records per thread, level after level (a fixed
-            # function of the chunk count alone)
-            # (one allocation: every level's records, then every level's segment bounds)
-            levels, m = [], n
-            while True:
-                n_seg = -(-m // _WSUM_SEG)
-                levels.append((n_seg, np.minimum(np.arange(n_seg + 1, dtype=np.int64) * _WSUM_SEG, m)))
-                if n_seg == 1:
-                    break
-                m = n_seg
-            segs = np.concatenate([seg for _, seg in levels])
-            n_rec = n + sum(n_seg for n_seg, _ in levels[:-1])
-            work = DeviceBuffer(ctx, n_rec * nb + segs.nbytes)
-            keep.append(work)
-            cur, sptr = work.ptr, work.ptr + n_rec * nb
-            ctx.h2d(sptr, segs, st)
-            reduce_axes(None, cur, st)
-            nxt = cur + n * nb
-            for n_seg, seg in levels:
-                dst = fin.ptr if n_seg == 1 else nxt
-                engine.wsum_combine_segments(ctx, cur, None, sptr, n_seg, dst, st)
-                cur, nxt, sptr = dst, dst + n_seg * nb, sptr + seg.nbytes
-        elif dims is not None:
-            out_off, tables = self._grid_from_dims(dims, axes, final_shape)
-            obuf = DeviceBuffer(ctx, out_off.nbytes)
-            ctx.h2d(obuf.ptr, out_off, st)
-            tbuf = DeviceBuffer(ctx, max(tables["blob"].nbytes, 16))
-            ctx.h2d(tbuf.ptr, tables["blob"], st)
-            g = _lib.Grid()
-            g.ndim = ds.ndim
-            g.axes_mask = axes_mask
-            for d in range(ds.ndim):
-                g.n_coords[d] = tables["n_coords"][d]
-                g.out_extent[d] = final_shape[d] if d not in axes else 1
-                if d not in axes:
-                    g.pos_coord[d] = tbuf.ptr + 4 * tables["pos_coord"][d]
-                    g.pos_local[d] = tbuf.ptr + 4 * tables["pos_local"][d]
-                    g.coord_count[d] = tbuf.ptr + 4 * tables["coord_count"][d]
-            g.chunk_out_offsets = obuf.ptr
-            parts = DeviceBuffer(ctx, max(int(tables["n_parts"]), 1) * nb)
-            reduce_axes(obuf.ptr, parts.ptr, st)
-            engine.wsum_combine_grid(ctx, parts.ptr, g, fin.ptr, st)
-            keep += [obuf, tbuf, parts]
-        else:
-            sizes, fidx = [], []
-            for _, projs in chunk_list:
-                pos = [p.out_pos if i not in axes else np.zeros(1, dtype=np.int64) for i, p in enumerate(projs)]
-                grids = np.meshgrid(*pos, indexing="ij")
-                fidx.append(np.ravel_multi_index([x.reshape(-1) for x in grids], final_shape))
-                sizes.append(grids[0].size)
-            out_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-            f_all = np.concatenate(fidx)
-            order = np.argsort(f_all, kind="stable").astype(np.int64)
-            seg = np.searchsorted(f_all[order], np.arange(n_final + 1)).astype(np.int64)
-            meta = np.concatenate([out_off[:-1], order, seg])
-            mbuf = DeviceBuffer(ctx, meta.nbytes)
-            ctx.h2d(mbuf.ptr, meta, st)
-            parts = DeviceBuffer(ctx, max(int(out_off[-1]), 1) * nb)
-            reduce_axes(mbuf.ptr, parts.ptr, st)
-            engine.wsum_combine_segments(ctx, parts.ptr, mbuf.ptr + 8 * n, mbuf.ptr + 8 * (n + order.size),
-                                            n_final, fin.ptr, st)
-            keep += [mbuf, parts]
-        ctx.d2h(final, fin.ptr, st)
-        ctx.synchronize(st)
-        del keep
-        return fmt(final.reshape(final_shape))
+        fin, keep = self._reduce_records(q, axes, _lib.WSUM_NBYTES, launch, engine.wsum_combine_segments,
+                                         engine.wsum_combine_grid)
+        return self._format_weighted(self._records_back(q, fin, keep, engine.wsum_dtype))
 
     def _format_moments(self, parts):
         """The float64 result of a var / std query from its combined records
@@ -2063,9 +1826,7 @@ class Active:
         ds = self.ds
         dt = ds.dtype
         n_final = int(np.prod(final_shape))
-        axes_mask = 0
-        for a in axes:
-            axes_mask |= 1 << a
+        axes_mask = _axes_mask(axes)
         out_off, tables = grid
         n_all = out_off.size
         n_parts_all = int(tables["n_parts"])
@@ -2083,17 +1844,7 @@ class Active:
         ctx.h2d(abuf.ptr, all_off, st)
         tbuf = DeviceBuffer(ctx, max(tables["blob"].nbytes, 16))
         ctx.h2d(tbuf.ptr, tables["blob"], st)
-        g = _lib.Grid()
-        g.ndim = ds.ndim
-        g.axes_mask = axes_mask
-        for d in range(ds.ndim):
-            g.n_coords[d] = tables["n_coords"][d]
-            g.out_extent[d] = final_shape[d] if d not in axes else 1
-            if d not in axes:
-                g.pos_coord[d] = tbuf.ptr + 4 * tables["pos_coord"][d]
-                g.pos_local[d] = tbuf.ptr + 4 * tables["pos_local"][d]
-                g.coord_count[d] = tbuf.ptr + 4 * tables["coord_count"][d]
-        g.chunk_out_offsets = abuf.ptr
+        g = _grid_struct(ds.ndim, axes, final_shape, tables, tbuf.ptr, abuf.ptr)
         fin = DeviceBuffer(ctx, max(n_final, 1) * _lib.PARTIAL_NBYTES)
         folded = fused = False
         zs_ok = self._fold_sign_ok(axes)
@@ -2261,27 +2012,12 @@ class Active:
         if len(axes) == ds.ndim:
             final = self._total(plan, st)
             return self._format(final.reshape(final_shape), final_shape)
-        axes_mask = 0
-        for a in axes:
-            axes_mask |= 1 << a
+        axes_mask = _axes_mask(axes)
         grid = self._grid_tables(chunk_list, axes, final_shape)
         if grid is not None:
             return self._grid_combine(ctx, st, plan, grid, axes, final_shape)
         # general case: per-chunk partial arrays, then a segmented device combine
-        sizes, fidx = [], []
-        for _, projs in chunk_list:
-            pos = [p.out_pos if i not in axes else np.zeros(1, dtype=np.int64)
-                   for i, p in enumerate(projs)]
-            grids = np.meshgrid(*pos, indexing="ij")
-            fidx.append(np.ravel_multi_index([g.reshape(-1) for g in grids], final_shape))
-            sizes.append(grids[0].size)
-        out_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-        f_all = np.concatenate(fidx)
-        order = np.argsort(f_all, kind="stable").astype(np.int64)
-        seg = np.searchsorted(f_all[order], np.arange(n_final + 1)).astype(np.int64)
-        axes_mask = 0
-        for a in axes:
-            axes_mask |= 1 << a
+        out_off, order, seg = _segment_meta((projs for _, projs in chunk_list), axes, final_shape)
         meta = np.concatenate([out_off[:-1], order, seg])
         mbuf = DeviceBuffer(ctx, meta.nbytes)
         ctx.h2d(mbuf.ptr, meta, st)

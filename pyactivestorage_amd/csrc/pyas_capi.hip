@@ -244,6 +244,92 @@ int combine_into(int dtype, const pyas_partial *in, int64_t n, uint32_t flags, p
     return PYAS_OK;
 }
 
+// The pyas_grid of a grid combine: its extents and tables, with the outputs
+// and the chunk layers per output it describes (rank and axes mask checked).
+int check_grid(const pyas_grid *g, int64_t &n_out, int64_t &n_layers) {
+    n_out = n_layers = 1;
+    for (int d = 0; d < g->ndim; ++d) {
+        if (g->n_coords[d] < 1) return fail(PYAS_EINVAL, "n_coords[%d] = %lld", d, (long long)g->n_coords[d]);
+        if ((g->axes_mask >> d) & 1u) {
+            n_layers *= g->n_coords[d];
+        } else {
+            if (g->out_extent[d] < 1) return fail(PYAS_EINVAL, "out_extent[%d] = %lld", d, (long long)g->out_extent[d]);
+            if (!g->pos_coord[d] || !g->pos_local[d] || !g->coord_count[d])
+                return fail(PYAS_EINVAL, "kept dim %d has a NULL table", d);
+            n_out *= g->out_extent[d];
+        }
+    }
+    return PYAS_OK;
+}
+
+// pyas_*_combine_grid of the statistics' records: `launch` is launch_*_grid.
+template <typename R>
+int combine_grid_records(pyas_ctx *ctx, const R *in, const pyas_grid *g, R *out, void *stream,
+                         hipError_t (*launch)(const R *, const pyas_grid &, int64_t, int64_t, R *, hipStream_t)) {
+    if (!ctx) return fail(PYAS_EINVAL, "ctx is NULL");
+    if (!g) return fail(PYAS_EINVAL, "grid is NULL");
+    if (g->ndim < 1 || g->ndim > PYAS_MAX_DIMS)
+        return fail(PYAS_ENOTSUP, "grid rank %d outside 1..%d", g->ndim, PYAS_MAX_DIMS);
+    if (g->axes_mask >> g->ndim) return fail(PYAS_EINVAL, "axes mask 0x%x beyond rank %d", g->axes_mask, g->ndim);
+    int64_t n_out, n_layers;
+    const int rc = check_grid(g, n_out, n_layers);
+    if (rc) return rc;
+    if (!in || !out || !g->chunk_out_offsets) return fail(PYAS_EINVAL, "NULL argument");
+    PYAS_HIP(hipSetDevice(ctx->device));
+    PYAS_HIP(launch(in, *g, n_out, n_layers, out, (hipStream_t)stream));
+    return PYAS_OK;
+}
+
+// pyas_*_combine_segments of the statistics' records (`index` may be NULL:
+// the records in order): `launch` is launch_*_segments.
+template <typename R>
+int combine_segments_records(pyas_ctx *ctx, const R *in, const int64_t *index, const int64_t *seg_offsets,
+                             int64_t n_segments, R *out, void *stream,
+                             hipError_t (*launch)(const R *, const int64_t *, const int64_t *, int64_t, R *,
+                                                  hipStream_t)) {
+    if (!ctx) return fail(PYAS_EINVAL, "ctx is NULL");
+    if (n_segments < 0) return fail(PYAS_EINVAL, "negative segment count");
+    if (n_segments == 0) return PYAS_OK;
+    if (!in || !seg_offsets || !out) return fail(PYAS_EINVAL, "NULL argument");
+    PYAS_HIP(hipSetDevice(ctx->device));
+    PYAS_HIP(launch(in, index, seg_offsets, n_segments, out, (hipStream_t)stream));
+    return PYAS_OK;
+}
+
+// A record reduction over every dim: a workgroup per (chunk, tile), the tiles
+// of a chunk merged in tile order from `tiles` (scratch of one R per
+// workgroup; NULL for one tile per chunk).
+template <typename R>
+int full_geometry(pyas_ctx *ctx, void *stream, int64_t n_chunks, int64_t chunk_bytes, int64_t &tpc, int64_t &grid,
+                  R *&tiles) {
+    tpc = tiles_per_chunk(ctx, chunk_bytes);
+    grid = n_chunks * tpc;
+    if (grid >= (int64_t(1) << 31)) return fail(PYAS_ENOTSUP, "grid of %lld workgroups", (long long)grid);
+    tiles = nullptr;
+    if (tpc > 1) {
+        void *scr = nullptr;
+        const int rc = ensure_scratch(ctx, stream, (size_t)grid * sizeof(R), &scr);
+        if (rc) return rc;
+        tiles = (R *)scr;
+    }
+    return PYAS_OK;
+}
+
+// A record reduction over some dims: `row` (the innermost dim is reduced) and
+// the workgroups per chunk.  Outputs per workgroup pass: a lane each
+// (innermost dim kept), or a wave each (innermost dim reduced; about 16
+// outputs per wave).
+void axes_geometry(int ndim, const int64_t *chunk_shape, uint32_t axes_mask, bool &row, int64_t &bpc) {
+    int64_t keep_elems = 1;
+    for (int d = 0; d < ndim; ++d)
+        if (!((axes_mask >> d) & 1u)) keep_elems *= chunk_shape[d];
+    row = ((axes_mask >> (ndim - 1)) & 1u) != 0;
+    const int64_t per_block = row ? (pyas::kBlock / pyas::kWave) * 16 : pyas::kBlock;
+    bpc = (keep_elems + per_block - 1) / per_block;
+    if (bpc > 64) bpc = 64;
+    if (bpc < 1) bpc = 1;
+}
+
 }  // namespace
 
 namespace pyas {
@@ -1455,18 +1541,9 @@ int pyas_combine_grid(pyas_ctx *ctx, int32_t dtype, const pyas_partial *in, cons
         }
         combine_flags |= pyas::kCombineThreadOnly;   // the per-thread form keys it
     }
-    int64_t n_out = 1, n_layers = 1;
-    for (int d = 0; d < g->ndim; ++d) {
-        if (g->n_coords[d] < 1) return fail(PYAS_EINVAL, "n_coords[%d] = %lld", d, (long long)g->n_coords[d]);
-        if ((g->axes_mask >> d) & 1u) {
-            n_layers *= g->n_coords[d];
-        } else {
-            if (g->out_extent[d] < 1) return fail(PYAS_EINVAL, "out_extent[%d] = %lld", d, (long long)g->out_extent[d]);
-            if (!g->pos_coord[d] || !g->pos_local[d] || !g->coord_count[d])
-                return fail(PYAS_EINVAL, "kept dim %d has a NULL table", d);
-            n_out *= g->out_extent[d];
-        }
-    }
+    int64_t n_out, n_layers;
+    const int rc = check_grid(g, n_out, n_layers);
+    if (rc) return rc;
     if (!in || !out || !g->chunk_out_offsets) return fail(PYAS_EINVAL, "NULL argument");
     if (ct.on && n_layers >= (int64_t(1) << 31))   // the keyed combine's 32-bit layer positions
         return fail(PYAS_ENOTSUP, "zero sign: more than 2^31 chunk layers");
@@ -1504,33 +1581,16 @@ int pyas_moments_axes(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *m
     x.masked = masked;
     if (axes_mask == (1u << batch->ndim) - 1u) {
         // every dim reduced: a workgroup per (chunk, tile); tiles merge in tile order
-        const int64_t tpc = tiles_per_chunk(ctx, x.r.chunk_elems * es);
-        const int64_t grid = n * tpc;
-        if (grid >= (int64_t(1) << 31)) return fail(PYAS_ENOTSUP, "grid of %lld workgroups", (long long)grid);
-        x.bpc = tpc;
-        if (tpc > 1) {
-            void *scr = nullptr;
-            rc = ensure_scratch(ctx, stream, (size_t)grid * sizeof(pyas_moments), &scr);
-            if (rc) return rc;
-            x.tiles = (pyas_moments *)scr;
-        }
+        int64_t grid;
+        rc = full_geometry(ctx, stream, n, x.r.chunk_elems * es, x.bpc, grid, x.tiles);
+        if (rc) return rc;
         PYAS_HIP(pyas::launch_moments_full(batch->dtype, x, shuf, grid, st));
-        if (tpc > 1) PYAS_HIP(pyas::launch_moments_tiles(x.tiles, tpc, n, out_offsets, out, st));
+        if (x.bpc > 1) PYAS_HIP(pyas::launch_moments_tiles(x.tiles, x.bpc, n, out_offsets, out, st));
         return PYAS_OK;
     }
     if (!out_offsets) return fail(PYAS_EINVAL, "out_offsets is NULL");
-    int64_t keep_elems = 1;
-    for (int d = 0; d < batch->ndim; ++d)
-        if (!((axes_mask >> d) & 1u)) keep_elems *= batch->chunk_shape[d];
-    x.row = ((axes_mask >> (batch->ndim - 1)) & 1u) != 0;
-    // outputs per workgroup pass: a lane each (innermost dim kept), or a wave
-    // each (innermost dim reduced; about 16 outputs per wave)
-    const int64_t per_block = x.row ? (pyas::kBlock / pyas::kWave) * 16 : pyas::kBlock;
-    int64_t bpc = (keep_elems + per_block - 1) / per_block;
-    if (bpc > 64) bpc = 64;
-    if (bpc < 1) bpc = 1;
-    x.bpc = bpc;
-    const int64_t grid = n * bpc;
+    axes_geometry(batch->ndim, batch->chunk_shape, axes_mask, x.row, x.bpc);
+    const int64_t grid = n * x.bpc;
     if (grid >= (int64_t(1) << 31)) return fail(PYAS_ENOTSUP, "grid too large");
     PYAS_HIP(pyas::launch_moments_axes(batch->dtype, x, shuf, grid, st));
     return PYAS_OK;
@@ -1539,38 +1599,13 @@ int pyas_moments_axes(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *m
 int pyas_moments_combine_segments(pyas_ctx *ctx, const pyas_moments *in, const int64_t *index,
                                   const int64_t *seg_offsets, int64_t n_segments, pyas_moments *out,
                                   void *stream) {
-    if (!ctx) return fail(PYAS_EINVAL, "ctx is NULL");
-    if (n_segments < 0) return fail(PYAS_EINVAL, "negative segment count");
-    if (n_segments == 0) return PYAS_OK;
-    if (!in || !seg_offsets || !out) return fail(PYAS_EINVAL, "NULL argument");
-    PYAS_HIP(hipSetDevice(ctx->device));
-    PYAS_HIP(pyas::launch_moments_segments(in, index, seg_offsets, n_segments, out, (hipStream_t)stream));
-    return PYAS_OK;
+    return combine_segments_records(ctx, in, index, seg_offsets, n_segments, out, stream,
+                                    pyas::launch_moments_segments);
 }
 
 int pyas_moments_combine_grid(pyas_ctx *ctx, const pyas_moments *in, const pyas_grid *g, pyas_moments *out,
                               void *stream) {
-    if (!ctx) return fail(PYAS_EINVAL, "ctx is NULL");
-    if (!g) return fail(PYAS_EINVAL, "grid is NULL");
-    if (g->ndim < 1 || g->ndim > PYAS_MAX_DIMS)
-        return fail(PYAS_ENOTSUP, "grid rank %d outside 1..%d", g->ndim, PYAS_MAX_DIMS);
-    if (g->axes_mask >> g->ndim) return fail(PYAS_EINVAL, "axes mask 0x%x beyond rank %d", g->axes_mask, g->ndim);
-    int64_t n_out = 1, n_layers = 1;
-    for (int d = 0; d < g->ndim; ++d) {
-        if (g->n_coords[d] < 1) return fail(PYAS_EINVAL, "n_coords[%d] = %lld", d, (long long)g->n_coords[d]);
-        if ((g->axes_mask >> d) & 1u) {
-            n_layers *= g->n_coords[d];
-        } else {
-            if (g->out_extent[d] < 1) return fail(PYAS_EINVAL, "out_extent[%d] = %lld", d, (long long)g->out_extent[d]);
-            if (!g->pos_coord[d] || !g->pos_local[d] || !g->coord_count[d])
-                return fail(PYAS_EINVAL, "kept dim %d has a NULL table", d);
-            n_out *= g->out_extent[d];
-        }
-    }
-    if (!in || !out || !g->chunk_out_offsets) return fail(PYAS_EINVAL, "NULL argument");
-    PYAS_HIP(hipSetDevice(ctx->device));
-    PYAS_HIP(pyas::launch_moments_grid(in, *g, n_out, n_layers, out, (hipStream_t)stream));
-    return PYAS_OK;
+    return combine_grid_records(ctx, in, g, out, stream, pyas::launch_moments_grid);
 }
 
 int pyas_comoments_axes(pyas_ctx *ctx, const pyas_batch *bx, const pyas_mask *mask_x, const pyas_batch *by,
@@ -1614,32 +1649,16 @@ int pyas_comoments_axes(pyas_ctx *ctx, const pyas_batch *bx, const pyas_mask *ma
     x.shuf_y = shy;
     if (axes_mask == (1u << bx->ndim) - 1u) {
         // every dim reduced: a workgroup per (chunk, tile) of one side's bytes; tiles merge in tile order
-        const int64_t tpc = tiles_per_chunk(ctx, x.x.chunk_elems * es);
-        const int64_t grid = n * tpc;
-        if (grid >= (int64_t(1) << 31)) return fail(PYAS_ENOTSUP, "grid of %lld workgroups", (long long)grid);
-        x.bpc = tpc;
-        if (tpc > 1) {
-            void *scr = nullptr;
-            rc = ensure_scratch(ctx, stream, (size_t)grid * sizeof(pyas_comoments), &scr);
-            if (rc) return rc;
-            x.tiles = (pyas_comoments *)scr;
-        }
+        int64_t grid;
+        rc = full_geometry(ctx, stream, n, x.x.chunk_elems * es, x.bpc, grid, x.tiles);
+        if (rc) return rc;
         PYAS_HIP(pyas::launch_comoments_full(bx->dtype, x, grid, st));
-        if (tpc > 1) PYAS_HIP(pyas::launch_comoments_tiles(x.tiles, tpc, n, out_offsets, out, st));
+        if (x.bpc > 1) PYAS_HIP(pyas::launch_comoments_tiles(x.tiles, x.bpc, n, out_offsets, out, st));
         return PYAS_OK;
     }
     if (!out_offsets) return fail(PYAS_EINVAL, "out_offsets is NULL");
-    int64_t keep_elems = 1;
-    for (int d = 0; d < bx->ndim; ++d)
-        if (!((axes_mask >> d) & 1u)) keep_elems *= bx->chunk_shape[d];
-    x.row = ((axes_mask >> (bx->ndim - 1)) & 1u) != 0;
-    // outputs per workgroup pass, as in pyas_moments_axes
-    const int64_t per_block = x.row ? (pyas::kBlock / pyas::kWave) * 16 : pyas::kBlock;
-    int64_t bpc = (keep_elems + per_block - 1) / per_block;
-    if (bpc > 64) bpc = 64;
-    if (bpc < 1) bpc = 1;
-    x.bpc = bpc;
-    const int64_t grid = n * bpc;
+    axes_geometry(bx->ndim, bx->chunk_shape, axes_mask, x.row, x.bpc);
+    const int64_t grid = n * x.bpc;
     if (grid >= (int64_t(1) << 31)) return fail(PYAS_ENOTSUP, "grid too large");
     PYAS_HIP(pyas::launch_comoments_axes(bx->dtype, x, grid, st));
     return PYAS_OK;
@@ -1648,39 +1667,13 @@ int pyas_comoments_axes(pyas_ctx *ctx, const pyas_batch *bx, const pyas_mask *ma
 int pyas_comoments_combine_segments(pyas_ctx *ctx, const pyas_comoments *in, const int64_t *index,
                                     const int64_t *seg_offsets, int64_t n_segments, pyas_comoments *out,
                                     void *stream) {
-    if (!ctx) return fail(PYAS_EINVAL, "ctx is NULL");
-    if (n_segments < 0) return fail(PYAS_EINVAL, "negative segment count");
-    if (n_segments == 0) return PYAS_OK;
-    if (!in || !seg_offsets || !out) return fail(PYAS_EINVAL, "NULL argument");
-    PYAS_HIP(hipSetDevice(ctx->device));
-    PYAS_HIP(pyas::launch_comoments_segments(in, index, seg_offsets, n_segments, out, (hipStream_t)stream));
-    return PYAS_OK;
+    return combine_segments_records(ctx, in, index, seg_offsets, n_segments, out, stream,
+                                    pyas::launch_comoments_segments);
 }
 
 int pyas_comoments_combine_grid(pyas_ctx *ctx, const pyas_comoments *in, const pyas_grid *g, pyas_comoments *out,
                                 void *stream) {
-    if (!ctx) return fail(PYAS_EINVAL, "ctx is NULL");
-    if (!g) return fail(PYAS_EINVAL, "grid is NULL");
-    if (g->ndim < 1 || g->ndim > PYAS_MAX_DIMS)
-        return fail(PYAS_ENOTSUP, "grid rank %d outside 1..%d", g->ndim, PYAS_MAX_DIMS);
-    if (g->axes_mask >> g->ndim) return fail(PYAS_EINVAL, "axes mask 0x%x beyond rank %d", g->axes_mask, g->ndim);
-    // (the checks of pyas_moments_combine_grid)
-    int64_t n_out = 1, n_layers = 1;
-    for (int d = 0; d < g->ndim; ++d) {
-        if (g->n_coords[d] < 1) return fail(PYAS_EINVAL, "n_coords[%d] = %lld", d, (long long)g->n_coords[d]);
-        if ((g->axes_mask >> d) & 1u) {
-            n_layers *= g->n_coords[d];
-        } else {
-            if (g->out_extent[d] < 1) return fail(PYAS_EINVAL, "out_extent[%d] = %lld", d, (long long)g->out_extent[d]);
-            if (!g->pos_coord[d] || !g->pos_local[d] || !g->coord_count[d])
-                return fail(PYAS_EINVAL, "kept dim %d has a NULL table", d);
-            n_out *= g->out_extent[d];
-        }
-    }
-    if (!in || !out || !g->chunk_out_offsets) return fail(PYAS_EINVAL, "NULL argument");
-    PYAS_HIP(hipSetDevice(ctx->device));
-    PYAS_HIP(pyas::launch_comoments_grid(in, *g, n_out, n_layers, out, (hipStream_t)stream));
-    return PYAS_OK;
+    return combine_grid_records(ctx, in, g, out, stream, pyas::launch_comoments_grid);
 }
 
 // pyas_trend_axes / pyas_trend_cols: the checks of the coordinate
@@ -1721,17 +1714,8 @@ int pyas_trend_axes(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mas
     x.cdim = coord->dim;
     x.shuf = shuf;
     x.bswap = bsw;
-    int64_t keep_elems = 1;
-    for (int d = 0; d < batch->ndim; ++d)
-        if (!((axes_mask >> d) & 1u)) keep_elems *= batch->chunk_shape[d];
-    x.row = ((axes_mask >> (batch->ndim - 1)) & 1u) != 0;
-    // outputs per workgroup pass, as in pyas_moments_axes (every dim reduced: one wave per chunk)
-    const int64_t per_block = x.row ? (pyas::kBlock / pyas::kWave) * 16 : pyas::kBlock;
-    int64_t bpc = (keep_elems + per_block - 1) / per_block;
-    if (bpc > 64) bpc = 64;
-    if (bpc < 1) bpc = 1;
-    x.bpc = bpc;
-    const int64_t grid = n * bpc;
+    axes_geometry(batch->ndim, batch->chunk_shape, axes_mask, x.row, x.bpc);   // (every dim reduced: one wave per chunk)
+    const int64_t grid = n * x.bpc;
     if (grid >= (int64_t(1) << 31)) return fail(PYAS_ENOTSUP, "grid too large");
     PYAS_HIP(pyas::launch_trend_axes(batch->dtype, x, grid, (hipStream_t)stream));
     return PYAS_OK;
@@ -1840,32 +1824,16 @@ int pyas_wsum_axes(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask
     x.masked = masked;
     if (axes_mask == (1u << batch->ndim) - 1u) {
         // every dim reduced: a workgroup per (chunk, tile); tiles merge in tile order
-        const int64_t tpc = tiles_per_chunk(ctx, x.r.chunk_elems * es);
-        const int64_t grid = n * tpc;
-        if (grid >= (int64_t(1) << 31)) return fail(PYAS_ENOTSUP, "grid of %lld workgroups", (long long)grid);
-        x.bpc = tpc;
-        if (tpc > 1) {
-            void *scr = nullptr;
-            rc = ensure_scratch(ctx, stream, (size_t)grid * sizeof(pyas_wsum), &scr);
-            if (rc) return rc;
-            x.tiles = (pyas_wsum *)scr;
-        }
+        int64_t grid;
+        rc = full_geometry(ctx, stream, n, x.r.chunk_elems * es, x.bpc, grid, x.tiles);
+        if (rc) return rc;
         PYAS_HIP(pyas::launch_wsum_full(batch->dtype, x, shuf, grid, st));
-        if (tpc > 1) PYAS_HIP(pyas::launch_wsum_tiles(x.tiles, tpc, n, out_offsets, out, st));
+        if (x.bpc > 1) PYAS_HIP(pyas::launch_wsum_tiles(x.tiles, x.bpc, n, out_offsets, out, st));
         return PYAS_OK;
     }
     if (!out_offsets) return fail(PYAS_EINVAL, "out_offsets is NULL");
-    int64_t keep_elems = 1;
-    for (int d = 0; d < batch->ndim; ++d)
-        if (!((axes_mask >> d) & 1u)) keep_elems *= batch->chunk_shape[d];
-    x.row = ((axes_mask >> (batch->ndim - 1)) & 1u) != 0;
-    // outputs per workgroup pass, as in pyas_moments_axes
-    const int64_t per_block = x.row ? (pyas::kBlock / pyas::kWave) * 16 : pyas::kBlock;
-    int64_t bpc = (keep_elems + per_block - 1) / per_block;
-    if (bpc > 64) bpc = 64;
-    if (bpc < 1) bpc = 1;
-    x.bpc = bpc;
-    const int64_t grid = n * bpc;
+    axes_geometry(batch->ndim, batch->chunk_shape, axes_mask, x.row, x.bpc);
+    const int64_t grid = n * x.bpc;
     if (grid >= (int64_t(1) << 31)) return fail(PYAS_ENOTSUP, "grid too large");
     PYAS_HIP(pyas::launch_wsum_axes(batch->dtype, x, shuf, grid, st));
     return PYAS_OK;
@@ -1873,39 +1841,13 @@ int pyas_wsum_axes(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask
 
 int pyas_wsum_combine_segments(pyas_ctx *ctx, const pyas_wsum *in, const int64_t *index,
                                const int64_t *seg_offsets, int64_t n_segments, pyas_wsum *out, void *stream) {
-    if (!ctx) return fail(PYAS_EINVAL, "ctx is NULL");
-    if (n_segments < 0) return fail(PYAS_EINVAL, "negative segment count");
-    if (n_segments == 0) return PYAS_OK;
-    if (!in || !seg_offsets || !out) return fail(PYAS_EINVAL, "NULL argument");
-    PYAS_HIP(hipSetDevice(ctx->device));
-    PYAS_HIP(pyas::launch_wsum_segments(in, index, seg_offsets, n_segments, out, (hipStream_t)stream));
-    return PYAS_OK;
+    return combine_segments_records(ctx, in, index, seg_offsets, n_segments, out, stream,
+                                    pyas::launch_wsum_segments);
 }
 
 int pyas_wsum_combine_grid(pyas_ctx *ctx, const pyas_wsum *in, const pyas_grid *g, pyas_wsum *out,
                            void *stream) {
-    // (the checks of pyas_moments_combine_grid)
-    if (!ctx) return fail(PYAS_EINVAL, "ctx is NULL");
-    if (!g) return fail(PYAS_EINVAL, "grid is NULL");
-    if (g->ndim < 1 || g->ndim > PYAS_MAX_DIMS)
-        return fail(PYAS_ENOTSUP, "grid rank %d outside 1..%d", g->ndim, PYAS_MAX_DIMS);
-    if (g->axes_mask >> g->ndim) return fail(PYAS_EINVAL, "axes mask 0x%x beyond rank %d", g->axes_mask, g->ndim);
-    int64_t n_out = 1, n_layers = 1;
-    for (int d = 0; d < g->ndim; ++d) {
-        if (g->n_coords[d] < 1) return fail(PYAS_EINVAL, "n_coords[%d] = %lld", d, (long long)g->n_coords[d]);
-        if ((g->axes_mask >> d) & 1u) {
-            n_layers *= g->n_coords[d];
-        } else {
-            if (g->out_extent[d] < 1) return fail(PYAS_EINVAL, "out_extent[%d] = %lld", d, (long long)g->out_extent[d]);
-            if (!g->pos_coord[d] || !g->pos_local[d] || !g->coord_count[d])
-                return fail(PYAS_EINVAL, "kept dim %d has a NULL table", d);
-            n_out *= g->out_extent[d];
-        }
-    }
-    if (!in || !out || !g->chunk_out_offsets) return fail(PYAS_EINVAL, "NULL argument");
-    PYAS_HIP(hipSetDevice(ctx->device));
-    PYAS_HIP(pyas::launch_wsum_grid(in, *g, n_out, n_layers, out, (hipStream_t)stream));
-    return PYAS_OK;
+    return combine_grid_records(ctx, in, g, out, stream, pyas::launch_wsum_grid);
 }
 
 // The launch shapes shared by the counting kernels (binned counts and the

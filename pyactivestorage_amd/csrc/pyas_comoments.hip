@@ -503,27 +503,12 @@ hipError_t launch_com_axes_t(const ComomentsArgs &a, int64_t grid, hipStream_t s
     return hipGetLastError();
 }
 
-#define PYAS_COM_DISPATCH(FN, ...)                                   \
-    switch (dtype) {                                                 \
-        case PYAS_I8: return FN<int8_t>(__VA_ARGS__);                \
-        case PYAS_U8: return FN<uint8_t>(__VA_ARGS__);               \
-        case PYAS_I16: return FN<int16_t>(__VA_ARGS__);              \
-        case PYAS_U16: return FN<uint16_t>(__VA_ARGS__);             \
-        case PYAS_I32: return FN<int32_t>(__VA_ARGS__);              \
-        case PYAS_U32: return FN<uint32_t>(__VA_ARGS__);             \
-        case PYAS_I64: return FN<int64_t>(__VA_ARGS__);              \
-        case PYAS_U64: return FN<uint64_t>(__VA_ARGS__);             \
-        case PYAS_F32: return FN<float>(__VA_ARGS__);                \
-        case PYAS_F64: return FN<double>(__VA_ARGS__);               \
-        default: return hipErrorInvalidValue;                        \
-    }
-
 hipError_t launch_comoments_full(int dtype, const ComomentsArgs &a, int64_t grid, hipStream_t st) {
-    PYAS_COM_DISPATCH(launch_com_full_t, a, grid, st)
+    PYAS_DISPATCH_DTYPE(launch_com_full_t, a, grid, st)
 }
 
 hipError_t launch_comoments_axes(int dtype, const ComomentsArgs &a, int64_t grid, hipStream_t st) {
-    PYAS_COM_DISPATCH(launch_com_axes_t, a, grid, st)
+    PYAS_DISPATCH_DTYPE(launch_com_axes_t, a, grid, st)
 }
 
 hipError_t launch_comoments_tiles(const pyas_comoments *tiles, int64_t tpc, int64_t n_chunks,

@@ -262,51 +262,12 @@ __global__ __launch_bounds__(kBlock) void k_hist_axes(HistArgs a) {
     }
 }
 
-template <typename T>
-hipError_t launch_hist_full_t(const HistArgs &a, bool shuf, int64_t grid, size_t lds, hipStream_t st) {
-    if constexpr (sizeof(T) > 1) {
-        if (shuf) {
-            hipLaunchKernelGGL((k_hist_full<T, true>), dim3((unsigned)grid), dim3(kBlock), lds, st, a);
-            return hipGetLastError();
-        }
-    }
-    hipLaunchKernelGGL((k_hist_full<T, false>), dim3((unsigned)grid), dim3(kBlock), lds, st, a);
-    return hipGetLastError();
-}
-
-template <typename T>
-hipError_t launch_hist_axes_t(const HistArgs &a, bool shuf, int64_t grid, hipStream_t st) {
-    if constexpr (sizeof(T) > 1) {
-        if (shuf) {
-            hipLaunchKernelGGL((k_hist_axes<T, true>), dim3((unsigned)grid), dim3(kBlock), 0, st, a);
-            return hipGetLastError();
-        }
-    }
-    hipLaunchKernelGGL((k_hist_axes<T, false>), dim3((unsigned)grid), dim3(kBlock), 0, st, a);
-    return hipGetLastError();
-}
-
-#define PYAS_HIST_DISPATCH(FN, ...)                                  \
-    switch (dtype) {                                                 \
-        case PYAS_I8: return FN<int8_t>(__VA_ARGS__);                \
-        case PYAS_U8: return FN<uint8_t>(__VA_ARGS__);               \
-        case PYAS_I16: return FN<int16_t>(__VA_ARGS__);              \
-        case PYAS_U16: return FN<uint16_t>(__VA_ARGS__);             \
-        case PYAS_I32: return FN<int32_t>(__VA_ARGS__);              \
-        case PYAS_U32: return FN<uint32_t>(__VA_ARGS__);             \
-        case PYAS_I64: return FN<int64_t>(__VA_ARGS__);              \
-        case PYAS_U64: return FN<uint64_t>(__VA_ARGS__);             \
-        case PYAS_F32: return FN<float>(__VA_ARGS__);                \
-        case PYAS_F64: return FN<double>(__VA_ARGS__);               \
-        default: return hipErrorInvalidValue;                        \
-    }
-
 hipError_t launch_hist_full(int dtype, const HistArgs &a, bool shuf, int64_t grid, size_t lds, hipStream_t st) {
-    PYAS_HIST_DISPATCH(launch_hist_full_t, a, shuf, grid, lds, st)
+    PYAS_DISPATCH_DTYPE(launch_shuf, PYAS_SHUF_KERNEL(k_hist_full), a, shuf, grid, lds, st)
 }
 
 hipError_t launch_hist_axes(int dtype, const HistArgs &a, bool shuf, int64_t grid, hipStream_t st) {
-    PYAS_HIST_DISPATCH(launch_hist_axes_t, a, shuf, grid, st)
+    PYAS_DISPATCH_DTYPE(launch_shuf, PYAS_SHUF_KERNEL(k_hist_axes), a, shuf, grid, 0, st)
 }
 
 }  // namespace pyas

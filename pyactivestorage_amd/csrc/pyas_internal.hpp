@@ -6,11 +6,46 @@
 #include <stdint.h>
 
 #include <string>
+#include <type_traits>
 
 #include "pyas.h"
 #include "pyas_device.hpp"
 
 namespace pyas {
+
+// The statistics' launchers (host code).  PYAS_DISPATCH_DTYPE returns
+// FN<T>(...) for the element type T of the `dtype` in scope.
+#define PYAS_DISPATCH_DTYPE(FN, ...)                                 \
+    switch (dtype) {                                                 \
+        case PYAS_I8: return FN<int8_t>(__VA_ARGS__);                \
+        case PYAS_U8: return FN<uint8_t>(__VA_ARGS__);               \
+        case PYAS_I16: return FN<int16_t>(__VA_ARGS__);              \
+        case PYAS_U16: return FN<uint16_t>(__VA_ARGS__);             \
+        case PYAS_I32: return FN<int32_t>(__VA_ARGS__);              \
+        case PYAS_U32: return FN<uint32_t>(__VA_ARGS__);             \
+        case PYAS_I64: return FN<int64_t>(__VA_ARGS__);              \
+        case PYAS_U64: return FN<uint64_t>(__VA_ARGS__);             \
+        case PYAS_F32: return FN<float>(__VA_ARGS__);                \
+        case PYAS_F64: return FN<double>(__VA_ARGS__);               \
+        default: return hipErrorInvalidValue;                        \
+    }
+
+// A kernel template K<T, SHUF> as a value launch_shuf can instantiate.
+#define PYAS_SHUF_KERNEL(K) [](auto t, auto s) { return (&K<decltype(t), decltype(s)::value>); }
+
+// K<T, true> over shuffled data of a dtype wider than a byte (one byte has
+// nothing to unshuffle: that instantiation does not exist), else K<T, false>.
+template <typename T, typename K, typename A>
+hipError_t launch_shuf(K kernel, const A &a, bool shuf, int64_t grid, size_t lds, hipStream_t st) {
+    if constexpr (sizeof(T) > 1) {
+        if (shuf) {
+            hipLaunchKernelGGL(kernel(T{}, std::true_type{}), dim3((unsigned)grid), dim3(kBlock), lds, st, a);
+            return hipGetLastError();
+        }
+    }
+    hipLaunchKernelGGL(kernel(T{}, std::false_type{}), dim3((unsigned)grid), dim3(kBlock), lds, st, a);
+    return hipGetLastError();
+}
 
 // Passed by value in the kernarg segment (a few hundred bytes).
 struct ReduceArgs {

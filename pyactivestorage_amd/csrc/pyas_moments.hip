@@ -21,23 +21,26 @@
 #include <hip/hip_runtime.h>
 
 #include "pyas_kernels.hpp"   // ldg16, unpack16, unshuffle16, RadixCounter, decompose, all_masked
+#include "pyas_records.hpp"   // the tile / segment / grid combines
 
 namespace pyas {
 
-// a then b (the order matters to the last bit, so every caller fixes it)
-__device__ __forceinline__ pyas_moments mom_merged(const pyas_moments &a, const pyas_moments &b) {
-    const double na = (double)a.count, nb = (double)b.count;
-    const double d = b.mean - a.mean;
-    const double w = nb / (na + nb);
-    pyas_moments r;
-    r.count = a.count + b.count;
-    r.mean = a.mean + d * w;
-    r.m2 = a.m2 + b.m2 + d * d * na * w;
-    r.reserved = 0;
-    if (b.count == 0) r = a;         // an empty side is skipped, not multiplied through
-    else if (a.count == 0) r = b;
-    return r;
-}
+struct MomMerge {
+    // a then b (the order matters to the last bit, so every caller fixes it)
+    static __device__ __forceinline__ pyas_moments merged(const pyas_moments &a, const pyas_moments &b) {
+        const double na = (double)a.count, nb = (double)b.count;
+        const double d = b.mean - a.mean;
+        const double w = nb / (na + nb);
+        pyas_moments r;
+        r.count = a.count + b.count;
+        r.mean = a.mean + d * w;
+        r.m2 = a.m2 + b.m2 + d * d * na * w;
+        r.reserved = 0;
+        if (b.count == 0) r = a;         // an empty side is skipped, not multiplied through
+        else if (a.count == 0) r = b;
+        return r;
+    }
+};
 
 struct MomAcc {
     double K, s1, s2;
@@ -97,7 +100,7 @@ __device__ __forceinline__ void mom_wave_merge(pyas_moments &p) {
         q.mean = shfl_xor(p.mean, m);
         q.m2 = shfl_xor(p.m2, m);
         q.reserved = 0;
-        p = (lane & m) ? mom_merged(q, p) : mom_merged(p, q);
+        p = (lane & m) ? MomMerge::merged(q, p) : MomMerge::merged(p, q);
     }
 }
 
@@ -109,7 +112,7 @@ __device__ __forceinline__ void mom_block_merge(pyas_moments &p) {
     __syncthreads();
     if (threadIdx.x == 0) {
 #pragma unroll
-        for (int k = 1; k < kBlock / kWave; ++k) p = mom_merged(p, s_w[k]);
+        for (int k = 1; k < kBlock / kWave; ++k) p = MomMerge::merged(p, s_w[k]);
     }
 }
 
@@ -413,153 +416,30 @@ __global__ __launch_bounds__(kBlock) void k_moments_axes(MomentsArgs a) {
 }
 
 // ---------------------------------------------------------------------------
-// combines: one thread per output, sequential fixed order
+// launchers
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void k_moments_tiles(const pyas_moments *tiles, int64_t tpc, int64_t n_chunks,
-                                                          const int64_t *out_offsets, pyas_moments *out) {
-    const int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (c >= n_chunks) return;
-    pyas_moments p = tiles[c * tpc];
-    for (int64_t t = 1; t < tpc; ++t) p = mom_merged(p, tiles[c * tpc + t]);
-    out[out_offsets ? out_offsets[c] : c] = p;
-}
-
-__global__ __launch_bounds__(kBlock) void k_moments_segments(const pyas_moments *in, const int64_t *index,
-                                                             const int64_t *seg, int64_t n_seg, pyas_moments *out) {
-    const int64_t sidx = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (sidx >= n_seg) return;
-    pyas_moments p;
-    p.count = 0; p.mean = 0.0; p.m2 = 0.0; p.reserved = 0;
-    constexpr int U = 8;   // U records in flight, merged in index order
-    const int64_t k1 = seg[sidx + 1];
-    for (int64_t k0 = seg[sidx]; k0 < k1; k0 += U) {
-        pyas_moments q[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            q[u].count = 0; q[u].mean = 0.0; q[u].m2 = 0.0; q[u].reserved = 0;
-            if (k0 + u < k1) q[u] = in[index ? index[k0 + u] : k0 + u];
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) p = mom_merged(p, q[u]);
-    }
-    out[sidx] = p;
-}
-
-// the walk of k_combine_grid: output f's kept coordinates give the chunk
-// position and the index j in each chunk's record array; the layers follow in
-// C order over the reduced dims' chunk coordinates
-__global__ __launch_bounds__(kBlock) void k_moments_grid(const pyas_moments *in, pyas_grid g, int64_t n_out,
-                                                         int64_t n_layers, pyas_moments *out) {
-    const int64_t f = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (f >= n_out) return;
-    int64_t gstride[PYAS_MAX_DIMS], digit[PYAS_MAX_DIMS];
-    int64_t j = 0, jstride = 1, st = 1, n = 0, rest = f;
-#pragma unroll
-    for (int d = PYAS_MAX_DIMS - 1; d >= 0; --d) {
-        gstride[d] = st;
-        digit[d] = 0;
-        if (d < g.ndim) {
-            if (!((g.axes_mask >> d) & 1u)) {
-                const int64_t e = g.out_extent[d];
-                const int64_t p = rest % e;
-                rest /= e;
-                const int64_t ad = g.pos_coord[d][p];
-                n += ad * st;
-                j += (int64_t)g.pos_local[d][p] * jstride;
-                jstride *= g.coord_count[d][ad];
-            }
-            st *= g.n_coords[d];
-        }
-    }
-    pyas_moments p;
-    p.count = 0; p.mean = 0.0; p.m2 = 0.0; p.reserved = 0;
-    for (int64_t l = 0; l < n_layers; ++l) {
-        const int64_t off = g.chunk_out_offsets[n];
-        bool carry = true;
-#pragma unroll
-        for (int d = PYAS_MAX_DIMS - 1; d >= 0; --d) {
-            if (carry && d < g.ndim && ((g.axes_mask >> d) & 1u)) {
-                n += gstride[d];
-                if (++digit[d] == g.n_coords[d]) {
-                    digit[d] = 0;
-                    n -= g.n_coords[d] * gstride[d];
-                } else {
-                    carry = false;
-                }
-            }
-        }
-        p = mom_merged(p, in[off + j]);
-    }
-    out[f] = p;
-}
-
-template <typename T>
-hipError_t launch_full_t(const MomentsArgs &a, bool shuf, int64_t grid, hipStream_t st) {
-    if constexpr (sizeof(T) > 1) {
-        if (shuf) {
-            hipLaunchKernelGGL((k_moments_full<T, true>), dim3((unsigned)grid), dim3(kBlock), 0, st, a);
-            return hipGetLastError();
-        }
-    }
-    hipLaunchKernelGGL((k_moments_full<T, false>), dim3((unsigned)grid), dim3(kBlock), 0, st, a);
-    return hipGetLastError();
-}
-
-template <typename T>
-hipError_t launch_axes_m_t(const MomentsArgs &a, bool shuf, int64_t grid, hipStream_t st) {
-    if constexpr (sizeof(T) > 1) {
-        if (shuf) {
-            hipLaunchKernelGGL((k_moments_axes<T, true>), dim3((unsigned)grid), dim3(kBlock), 0, st, a);
-            return hipGetLastError();
-        }
-    }
-    hipLaunchKernelGGL((k_moments_axes<T, false>), dim3((unsigned)grid), dim3(kBlock), 0, st, a);
-    return hipGetLastError();
-}
-
-#define PYAS_MOM_DISPATCH(FN, ...)                                   \
-    switch (dtype) {                                                 \
-        case PYAS_I8: return FN<int8_t>(__VA_ARGS__);                \
-        case PYAS_U8: return FN<uint8_t>(__VA_ARGS__);               \
-        case PYAS_I16: return FN<int16_t>(__VA_ARGS__);              \
-        case PYAS_U16: return FN<uint16_t>(__VA_ARGS__);             \
-        case PYAS_I32: return FN<int32_t>(__VA_ARGS__);              \
-        case PYAS_U32: return FN<uint32_t>(__VA_ARGS__);             \
-        case PYAS_I64: return FN<int64_t>(__VA_ARGS__);              \
-        case PYAS_U64: return FN<uint64_t>(__VA_ARGS__);             \
-        case PYAS_F32: return FN<float>(__VA_ARGS__);                \
-        case PYAS_F64: return FN<double>(__VA_ARGS__);               \
-        default: return hipErrorInvalidValue;                        \
-    }
-
 hipError_t launch_moments_full(int dtype, const MomentsArgs &a, bool shuf, int64_t grid, hipStream_t st) {
-    PYAS_MOM_DISPATCH(launch_full_t, a, shuf, grid, st)
+    PYAS_DISPATCH_DTYPE(launch_shuf, PYAS_SHUF_KERNEL(k_moments_full), a, shuf, grid, 0, st)
 }
 
 hipError_t launch_moments_axes(int dtype, const MomentsArgs &a, bool shuf, int64_t grid, hipStream_t st) {
-    PYAS_MOM_DISPATCH(launch_axes_m_t, a, shuf, grid, st)
+    PYAS_DISPATCH_DTYPE(launch_shuf, PYAS_SHUF_KERNEL(k_moments_axes), a, shuf, grid, 0, st)
 }
 
+// the combines: pyas_records.hpp over the record and MomMerge
 hipError_t launch_moments_tiles(const pyas_moments *tiles, int64_t tpc, int64_t n_chunks,
                                 const int64_t *out_offsets, pyas_moments *out, hipStream_t st) {
-    const int64_t nb = (n_chunks + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL(k_moments_tiles, dim3((unsigned)nb), dim3(kBlock), 0, st, tiles, tpc, n_chunks, out_offsets,
-                       out);
-    return hipGetLastError();
+    return launch_rec_tiles<pyas_moments, MomMerge>(tiles, tpc, n_chunks, out_offsets, out, st);
 }
 
 hipError_t launch_moments_segments(const pyas_moments *in, const int64_t *index, const int64_t *seg,
                                    int64_t n_seg, pyas_moments *out, hipStream_t st) {
-    const int64_t nb = (n_seg + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL(k_moments_segments, dim3((unsigned)nb), dim3(kBlock), 0, st, in, index, seg, n_seg, out);
-    return hipGetLastError();
+    return launch_rec_segments<pyas_moments, MomMerge>(in, index, seg, n_seg, out, st);
 }
 
 hipError_t launch_moments_grid(const pyas_moments *in, const pyas_grid &g, int64_t n_out, int64_t n_layers,
                                pyas_moments *out, hipStream_t st) {
-    const int64_t nb = (n_out + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL(k_moments_grid, dim3((unsigned)nb), dim3(kBlock), 0, st, in, g, n_out, n_layers, out);
-    return hipGetLastError();
+    return launch_rec_grid<pyas_moments, MomMerge>(in, g, n_out, n_layers, out, st);
 }
 
 }  // namespace pyas

@@ -1,8 +1,7 @@
 // pyas_records.hpp — the three combines of f64 records, written over the
-// record and its merge.  The weighted sums (pyas_weighted.hip, 32 bytes) and
-// the co-moments (pyas_comoments.hip, 48 bytes) use them;
-// pyas_moments.hip keeps its own copies of the same walks (k_moments_tiles,
-// k_moments_segments, k_moments_grid), which can move here unchanged.
+// record and its merge.  The second moments (pyas_moments.hip, 32 bytes), the
+// weighted sums (pyas_weighted.hip, 32 bytes) and the co-moments
+// (pyas_comoments.hip, 48 bytes; pyas_trend.hip's records too) use them.
 // One thread per output folds its records sequentially in a fixed order: tiles
 // in tile order, a segment in index order (pyas_combine_segments), chunk layers
 // in C order over the reduced dims' chunk coordinates (pyas_combine_grid).

@@ -275,51 +275,12 @@ __global__ __launch_bounds__(kBlock) void k_qsel_totals(const unsigned long long
     }
 }
 
-template <typename T>
-hipError_t launch_qsel_full_t(const QselArgs &a, bool shuf, int64_t grid, size_t lds, hipStream_t st) {
-    if constexpr (sizeof(T) > 1) {
-        if (shuf) {
-            hipLaunchKernelGGL((k_qsel_full<T, true>), dim3((unsigned)grid), dim3(kBlock), lds, st, a);
-            return hipGetLastError();
-        }
-    }
-    hipLaunchKernelGGL((k_qsel_full<T, false>), dim3((unsigned)grid), dim3(kBlock), lds, st, a);
-    return hipGetLastError();
-}
-
-template <typename T>
-hipError_t launch_qsel_axes_t(const QselArgs &a, bool shuf, int64_t grid, hipStream_t st) {
-    if constexpr (sizeof(T) > 1) {
-        if (shuf) {
-            hipLaunchKernelGGL((k_qsel_axes<T, true>), dim3((unsigned)grid), dim3(kBlock), 0, st, a);
-            return hipGetLastError();
-        }
-    }
-    hipLaunchKernelGGL((k_qsel_axes<T, false>), dim3((unsigned)grid), dim3(kBlock), 0, st, a);
-    return hipGetLastError();
-}
-
-#define PYAS_QSEL_DISPATCH(FN, ...)                                  \
-    switch (dtype) {                                                 \
-        case PYAS_I8: return FN<int8_t>(__VA_ARGS__);                \
-        case PYAS_U8: return FN<uint8_t>(__VA_ARGS__);               \
-        case PYAS_I16: return FN<int16_t>(__VA_ARGS__);              \
-        case PYAS_U16: return FN<uint16_t>(__VA_ARGS__);             \
-        case PYAS_I32: return FN<int32_t>(__VA_ARGS__);              \
-        case PYAS_U32: return FN<uint32_t>(__VA_ARGS__);             \
-        case PYAS_I64: return FN<int64_t>(__VA_ARGS__);              \
-        case PYAS_U64: return FN<uint64_t>(__VA_ARGS__);             \
-        case PYAS_F32: return FN<float>(__VA_ARGS__);                \
-        case PYAS_F64: return FN<double>(__VA_ARGS__);               \
-        default: return hipErrorInvalidValue;                        \
-    }
-
 hipError_t launch_qsel_full(int dtype, const QselArgs &a, bool shuf, int64_t grid, size_t lds, hipStream_t st) {
-    PYAS_QSEL_DISPATCH(launch_qsel_full_t, a, shuf, grid, lds, st)
+    PYAS_DISPATCH_DTYPE(launch_shuf, PYAS_SHUF_KERNEL(k_qsel_full), a, shuf, grid, lds, st)
 }
 
 hipError_t launch_qsel_axes(int dtype, const QselArgs &a, bool shuf, int64_t grid, hipStream_t st) {
-    PYAS_QSEL_DISPATCH(launch_qsel_axes_t, a, shuf, grid, st)
+    PYAS_DISPATCH_DTYPE(launch_shuf, PYAS_SHUF_KERNEL(k_qsel_axes), a, shuf, grid, 0, st)
 }
 
 hipError_t launch_qsel_step(const unsigned long long *table, int64_t n_rows, int32_t bits, const int64_t *rank,

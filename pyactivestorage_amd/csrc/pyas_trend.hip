@@ -503,39 +503,12 @@ hipError_t launch_tr_axes_t(const TrendArgs &a, int64_t grid, hipStream_t st) {
     return hipGetLastError();
 }
 
-template <typename T>
-hipError_t launch_tr_cols_t(const TrendColsArgs &a, bool shuf, int64_t grid, hipStream_t st) {
-    if constexpr (sizeof(T) > 1) {
-        if (shuf) {
-            hipLaunchKernelGGL((k_trend_cols<T, true>), dim3((unsigned)grid), dim3(kBlock), 0, st, a);
-            return hipGetLastError();
-        }
-    }
-    hipLaunchKernelGGL((k_trend_cols<T, false>), dim3((unsigned)grid), dim3(kBlock), 0, st, a);
-    return hipGetLastError();
-}
-
-#define PYAS_TREND_DISPATCH(FN, ...)                                 \
-    switch (dtype) {                                                 \
-        case PYAS_I8: return FN<int8_t>(__VA_ARGS__);                \
-        case PYAS_U8: return FN<uint8_t>(__VA_ARGS__);               \
-        case PYAS_I16: return FN<int16_t>(__VA_ARGS__);              \
-        case PYAS_U16: return FN<uint16_t>(__VA_ARGS__);             \
-        case PYAS_I32: return FN<int32_t>(__VA_ARGS__);              \
-        case PYAS_U32: return FN<uint32_t>(__VA_ARGS__);             \
-        case PYAS_I64: return FN<int64_t>(__VA_ARGS__);              \
-        case PYAS_U64: return FN<uint64_t>(__VA_ARGS__);             \
-        case PYAS_F32: return FN<float>(__VA_ARGS__);                \
-        case PYAS_F64: return FN<double>(__VA_ARGS__);               \
-        default: return hipErrorInvalidValue;                        \
-    }
-
 hipError_t launch_trend_axes(int dtype, const TrendArgs &a, int64_t grid, hipStream_t st) {
-    PYAS_TREND_DISPATCH(launch_tr_axes_t, a, grid, st)
+    PYAS_DISPATCH_DTYPE(launch_tr_axes_t, a, grid, st)
 }
 
 hipError_t launch_trend_cols(int dtype, const TrendColsArgs &a, bool shuf, int64_t grid, hipStream_t st) {
-    PYAS_TREND_DISPATCH(launch_tr_cols_t, a, shuf, grid, st)
+    PYAS_DISPATCH_DTYPE(launch_shuf, PYAS_SHUF_KERNEL(k_trend_cols), a, shuf, grid, 0, st)
 }
 
 hipError_t launch_trend_finalize(const pyas_comoments *in, int64_t n, int32_t what, double *value, uint8_t *masked,

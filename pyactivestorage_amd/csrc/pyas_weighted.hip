@@ -544,51 +544,12 @@ __global__ __launch_bounds__(kBlock) void k_wsum_axes(WsumArgs a) {
     }
 }
 
-template <typename T>
-hipError_t launch_wfull_t(const WsumArgs &a, bool shuf, int64_t grid, hipStream_t st) {
-    if constexpr (sizeof(T) > 1) {
-        if (shuf) {
-            hipLaunchKernelGGL((k_wsum_full<T, true>), dim3((unsigned)grid), dim3(kBlock), 0, st, a);
-            return hipGetLastError();
-        }
-    }
-    hipLaunchKernelGGL((k_wsum_full<T, false>), dim3((unsigned)grid), dim3(kBlock), 0, st, a);
-    return hipGetLastError();
-}
-
-template <typename T>
-hipError_t launch_waxes_t(const WsumArgs &a, bool shuf, int64_t grid, hipStream_t st) {
-    if constexpr (sizeof(T) > 1) {
-        if (shuf) {
-            hipLaunchKernelGGL((k_wsum_axes<T, true>), dim3((unsigned)grid), dim3(kBlock), 0, st, a);
-            return hipGetLastError();
-        }
-    }
-    hipLaunchKernelGGL((k_wsum_axes<T, false>), dim3((unsigned)grid), dim3(kBlock), 0, st, a);
-    return hipGetLastError();
-}
-
-#define PYAS_WSUM_DISPATCH(FN, ...)                                  \
-    switch (dtype) {                                                 \
-        case PYAS_I8: return FN<int8_t>(__VA_ARGS__);                \
-        case PYAS_U8: return FN<uint8_t>(__VA_ARGS__);               \
-        case PYAS_I16: return FN<int16_t>(__VA_ARGS__);              \
-        case PYAS_U16: return FN<uint16_t>(__VA_ARGS__);             \
-        case PYAS_I32: return FN<int32_t>(__VA_ARGS__);              \
-        case PYAS_U32: return FN<uint32_t>(__VA_ARGS__);             \
-        case PYAS_I64: return FN<int64_t>(__VA_ARGS__);              \
-        case PYAS_U64: return FN<uint64_t>(__VA_ARGS__);             \
-        case PYAS_F32: return FN<float>(__VA_ARGS__);                \
-        case PYAS_F64: return FN<double>(__VA_ARGS__);               \
-        default: return hipErrorInvalidValue;                        \
-    }
-
 hipError_t launch_wsum_full(int dtype, const WsumArgs &a, bool shuf, int64_t grid, hipStream_t st) {
-    PYAS_WSUM_DISPATCH(launch_wfull_t, a, shuf, grid, st)
+    PYAS_DISPATCH_DTYPE(launch_shuf, PYAS_SHUF_KERNEL(k_wsum_full), a, shuf, grid, 0, st)
 }
 
 hipError_t launch_wsum_axes(int dtype, const WsumArgs &a, bool shuf, int64_t grid, hipStream_t st) {
-    PYAS_WSUM_DISPATCH(launch_waxes_t, a, shuf, grid, st)
+    PYAS_DISPATCH_DTYPE(launch_shuf, PYAS_SHUF_KERNEL(k_wsum_axes), a, shuf, grid, 0, st)
 }
 
 hipError_t launch_wsum_tiles(const pyas_wsum *tiles, int64_t tpc, int64_t n_chunks, const int64_t *out_offsets,

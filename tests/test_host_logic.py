@@ -351,3 +351,201 @@ def test_dense_classes(rows, dense, none):
     p.sel_table_host = _sel_table(rows)
     ReductionPlan._dense_class(p)
     assert p._dense_boxes == dense and p._no_dense == none
+
+
+# -- the record-query driver of Active (var, weighted, cov, trend) ---------------
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 64 * 64, 64 * 64 + 1])
+def test_fold_levels(n):
+    """The chunk-order fold of a full record reduction: 64 records per thread,
+    level after level, down to one record."""
+    from pyactivestorage_amd.active import _RECORD_SEG, _fold_levels
+    assert _RECORD_SEG == 64
+    levels, n_rec = _fold_levels(n)
+    m = n
+    for k, (n_seg, bounds) in enumerate(levels):
+        assert n_seg == -(-m // 64)
+        assert bounds.dtype == np.int64 and bounds.shape == (n_seg + 1,)
+        assert bounds[0] == 0 and bounds[-1] == m and (np.diff(bounds) >= 0).all()
+        assert (np.diff(bounds) <= 64).all()
+        assert (n_seg == 1) == (k == len(levels) - 1)      # one segment ends the fold, and only it
+        m = n_seg
+    assert levels[0][1][0] == 0 and levels[0][1][-1] == n     # the first level covers [0, n]
+    assert levels[-1][0] == 1
+    assert n_rec == n + sum(n_seg for n_seg, _ in levels[:-1])
+    assert len(levels) == (1 if n <= 64 else 2 if n <= 64 * 64 else 3)
+
+
+def _projs(*out_pos):
+    from types import SimpleNamespace
+    return [SimpleNamespace(out_pos=np.array(p, dtype=np.int64)) for p in out_pos]
+
+
+def test_segment_meta():
+    """Two chunks along a kept dim (2 + 1 positions), two along a reduced dim,
+    one index-list dim (3 selected positions in one chunk), chunks in C
+    order: final shape (3, 1, 3)."""
+    from pyactivestorage_amd.active import _chunk_outputs, _segment_meta
+    rows, cols = [[0, 1], [2]], [0, 1, 2]
+    chunks = [_projs(rows[a], [7 + b], cols) for a in range(2) for b in range(2)]   # (the reduced dim's positions are not read)
+    final_shape = (3, 1, 3)
+    out_off, f_all = _chunk_outputs(chunks, (1,), final_shape)
+    assert out_off.dtype == np.int64 and out_off.tolist() == [0, 6, 12, 15, 18]
+    assert f_all.dtype == np.int64
+    assert f_all.tolist() == [0, 1, 2, 3, 4, 5] * 2 + [6, 7, 8] * 2
+    out_off2, order, seg = _segment_meta(chunks, (1,), final_shape)
+    assert out_off2.tolist() == out_off.tolist()
+    assert order.dtype == np.int64 and seg.dtype == np.int64
+    assert order.tolist() == np.argsort(f_all, kind="stable").tolist()
+    assert order.tolist() == [0, 6, 1, 7, 2, 8, 3, 9, 4, 10, 5, 11, 12, 15, 13, 16, 14, 17]
+    assert seg.tolist() == list(range(0, 19, 2))           # every output: one record per chunk layer
+    chunk_of = np.searchsorted(out_off, np.arange(18), side="right") - 1
+    for f in range(9):
+        mine = order[seg[f]:seg[f + 1]]
+        assert (f_all[mine] == f).all()                     # seg partitions the records per output
+        assert chunk_of[mine].tolist() == ([0, 1] if f < 6 else [2, 3])   # in chunk order
+
+
+def test_grid_struct():
+    from pyactivestorage_amd.active import _grid_struct
+    tables = {"n_coords": [2, 2, 1], "pos_coord": {0: 0, 2: 8}, "pos_local": {0: 3, 2: 11},
+              "coord_count": {0: 6, 2: 14}}
+    g = _grid_struct(3, (1,), (3, 1, 3), tables, 0x1000, 0x2000)
+    assert (g.ndim, g.axes_mask, g.chunk_out_offsets) == (3, 0b010, 0x2000)
+    assert list(g.n_coords)[:3] == [2, 2, 1] and list(g.out_extent)[:3] == [3, 1, 3]
+    for d, (pc, pl, cc) in {0: (0, 3, 6), 2: (8, 11, 14)}.items():      # kept dims: tbuf + 4 * offset
+        assert (g.pos_coord[d], g.pos_local[d], g.coord_count[d]) == (0x1000 + 4 * pc, 0x1000 + 4 * pl, 0x1000 + 4 * cc)
+    assert g.pos_coord[1] is None and g.pos_local[1] is None and g.coord_count[1] is None   # reduced: extent 1, no tables
+    # the dense form (pyas_trend_cols): the chunk grid alone
+    g = _grid_struct(3, (0,), (1, 4, 6), {"n_coords": [5, 2, 2]}, None, None)
+    assert (g.ndim, g.axes_mask, g.chunk_out_offsets) == (3, 0b001, None)
+    assert list(g.n_coords)[:3] == [5, 2, 2] and list(g.out_extent)[:3] == [1, 4, 6]
+    assert not any(list(g.pos_coord)) and not any(list(g.pos_local)) and not any(list(g.coord_count))
+
+
+def _traced(monkeypatch):
+    """``Active`` with its ingest, its device buffers and plans and every
+    ``engine`` launch replaced by recorders: the list they append to."""
+    import itertools
+    from types import SimpleNamespace
+
+    from pyactivestorage_amd import active as mod
+    calls = []
+    ptrs = itertools.count(1 << 20, 1 << 20)
+
+    class Ctx:
+        def h2d(self, dst, src, st): calls.append(("h2d", st))
+        def d2h(self, dst, src, st): calls.append(("d2h", st))
+        def synchronize(self, st): calls.append(("synchronize", st))
+        def stream_wait(self, waiter, waitee): calls.append(("stream_wait", waiter, waitee))
+    ctx = Ctx()
+
+    def ingest(self, coords, compressor, filters):
+        calls.append(("ingest", self.ds.name, len(coords)))
+        return ctx, "st-" + self.ds.name, SimpleNamespace(ptr=next(ptrs)), np.zeros(len(coords), np.int64), 0
+
+    def plan(ctx_, dtype, chunks, ptr, offsets, **kw):
+        calls.append(("plan", "selections" if "selections" in kw else "table" if kw["sel_table"] is not None else "whole"))
+        return SimpleNamespace(batch=None, mask_up=SimpleNamespace(struct=None))
+    monkeypatch.setattr(mod.Active, "_ingest", ingest)
+    monkeypatch.setattr(mod, "ReductionPlan", plan)
+    monkeypatch.setattr(mod, "DeviceBuffer", lambda ctx_, nbytes: SimpleNamespace(ptr=next(ptrs)))
+    monkeypatch.setattr(mod, "get_context", lambda *a, **k: pytest.fail("a context was asked for"))
+
+    def axes(name):      # (..., out_offsets, out, stream): is there an offsets table?
+        return lambda *a: calls.append((name, a[-3] is not None, a[-1]))
+
+    def segments(name):  # (ctx, in, index, seg, n_seg, out, stream)
+        return lambda c, in_, index, seg, n_seg, out, st: calls.append((name, index is not None, n_seg, st))
+
+    def grid(name):
+        return lambda c, in_, g, out, st: calls.append((name, st))
+    for stat in ("moments", "wsum", "comoments"):
+        monkeypatch.setattr(mod.engine, stat + "_axes", axes(stat + "_axes"))
+        monkeypatch.setattr(mod.engine, stat + "_combine_segments", segments(stat + "_combine_segments"))
+        monkeypatch.setattr(mod.engine, stat + "_combine_grid", grid(stat + "_combine_grid"))
+    monkeypatch.setattr(mod.engine, "trend_axes", axes("trend_axes"))
+    monkeypatch.setattr(mod.engine, "trend_finalize", lambda *a: calls.append(("trend_finalize", a[3], a[-1])))
+    return calls
+
+
+def _record_var(name, attrs=None):
+    from pyactivestorage_amd.variable import ChunkedVariable
+    return ChunkedVariable(name=name, shape=(130, 6), chunks=(2, 3), dtype=np.dtype("<f4"), chunk_index={},
+                           attrs=attrs or {}, reader=lambda off, size: b"")
+
+
+# The three routes of a record query, as the code before the shared driver
+# made them (written down from it, call by call):
+#   full     every axis over 65 x 2 = 130 chunks: the fold's bounds go up, the per-chunk pass writes without an
+#            offsets table, then two levels of combine_segments without an index (3 segments, then 1)
+#   box      axis 0 reduced, axis 1 kept: the chunk offsets and the grid tables go up, the per-chunk pass, combine_grid
+#   general  a vector missing_value: per-chunk selections; the segment meta goes up, the per-chunk pass,
+#            combine_segments with an index over the 6 outputs
+# (An integer index raises IndexError before any route, so the per-chunk selections are reached the other way.)
+def _routes(stat, combine, st):
+    return {
+        "full": [("h2d", st), (stat + "_axes", False, st), (combine + "_combine_segments", False, 3, st),
+                 (combine + "_combine_segments", False, 1, st)],
+        "box": [("h2d", st), ("h2d", st), (stat + "_axes", True, st), (combine + "_combine_grid", st)],
+        "general": [("h2d", st), (stat + "_axes", True, st), (combine + "_combine_segments", True, 6, st)],
+    }
+
+
+_ROUTE_QUERY = {"full": (None, None, "whole"), "box": (0, None, "whole"),
+                "general": (0, {"missing_value": np.array([1.0, 2.0, 3.0], "<f4")}, "selections")}
+
+
+@pytest.mark.parametrize("route", ["full", "box", "general"])
+@pytest.mark.parametrize("stat", ["var", "wmean", "cov", "trend", "trend-components"])
+def test_record_routes_call_sequence(monkeypatch, stat, route):
+    from pyactivestorage_amd import active as mod
+    from pyactivestorage_amd.active import Active
+    calls = _traced(monkeypatch)
+    # (the dense column kernel declines: the walk's routes are what is pinned here)
+    monkeypatch.setattr(mod.engine, "trend_cols", lambda *a: calls.append(("trend_cols", a[-1])) or False)
+    axis, attrs, sel = _ROUTE_QUERY[route]
+    a = Active(_record_var("x", attrs))
+    st, n = "st-x", 130
+    head =[("ingest", "x", n), ("plan", sel)]
+    tail = [("d2h", st), ("synchronize", st)]
+    if stat == "var":
+        q = a.var(axis=axis)
+        body = _routes("moments", "moments", st)[route]
+    elif stat == "wmean":
+        q = a.mean(axis=axis, weights={0: np.ones(130)})
+        head += [("h2d", st), ("h2d", st)]                                   # the weight pool, the origins
+        body = _routes("wsum", "wsum", st)[route]
+    elif stat == "cov":
+        q = a.cov(Active(_record_var("y", attrs)), axis=axis)
+        head = [("ingest", "x", n), ("ingest", "y", n), ("stream_wait", st, "st-y"), ("plan", sel), ("plan", sel)]
+        body = _routes("comoments", "comoments", st)[route]
+    else:
+        a.components = stat == "trend-components"
+        q = a.trend(along=0, axis=axis)
+        head += [("h2d", st), ("h2d", st)]                                   # the coordinate, the origins
+        if route == "box":
+            head += [("trend_cols", st)]
+        body = _routes("trend", "comoments", st)[route]
+        if a.components:
+            tail = [("trend_finalize", _lib.TREND_SLOPE, st), ("trend_finalize", _lib.TREND_INTERCEPT, st),
+                    ("d2h", st), ("d2h", st), ("d2h", st), ("synchronize", st)]
+        else:
+            tail = [("trend_finalize", _lib.TREND_SLOPE, st), ("d2h", st), ("d2h", st), ("synchronize", st)]
+    q[...]
+    assert calls == head + body + tail
+    if stat.startswith("trend"):
+        assert a.trend_path == "walk"
+
+
+def test_trend_dense_route_call_sequence(monkeypatch):
+    """The dense column kernel takes the box query: no per-chunk pass, no combine."""
+    from pyactivestorage_amd import active as mod
+    from pyactivestorage_amd.active import Active
+    calls = _traced(monkeypatch)
+    monkeypatch.setattr(mod.engine, "trend_cols", lambda *a: calls.append(("trend_cols", a[-1])) or True)
+    a = Active(_record_var("x"))
+    st = "st-x"
+    a.trend(along=0, axis=0)[...]
+    assert calls == [("ingest", "x", 130), ("plan", "whole"), ("h2d", st), ("h2d", st), ("trend_cols", st),
+                     ("trend_finalize", _lib.TREND_SLOPE, st), ("d2h", st), ("d2h", st), ("synchronize", st)]
+    assert a.trend_path == "cols"

@@ -35,16 +35,19 @@ K_COM_ROFF = _const("kComRoff", _text("pyas_comoments.hip"))
 def test_launch_cap_is_the_launchers():
     """The five launchers still cap the workgroups per chunk at LAUNCH_CAP."""
     capi = _text("pyas_capi.hip")
-    for fn in ("pyas_moments_axes", "pyas_comoments_axes", "pyas_wsum_axes", "hist_axes_shape"):
-        start = re.search(rf"^(static )?int(64_t)? {fn}\(", capi, re.M)
+    for fn in ("axes_geometry", "hist_axes_shape"):    # the two launch shapes
+        start = re.search(rf"^(static )?(void|int64_t) {fn}\(", capi, re.M)
         assert start, fn
         body = capi[start.end():]
         body = body[:re.search(r"^}", body, re.M).start()]
         assert re.search(rf"if \(bpc > {G.LAUNCH_CAP}\) bpc = {G.LAUNCH_CAP};", body), fn
-    for fn in ("pyas_hist_axes", "pyas_select_axes"):
-        start = re.search(rf"^int {fn}\(", capi, re.M)
-        body = capi[start.end():]
-        assert "hist_axes_shape(" in body[:re.search(r"^}", body, re.M).start()], fn
+    for shape, fns in (("axes_geometry", ("pyas_moments_axes", "pyas_comoments_axes", "pyas_wsum_axes")),
+                       ("hist_axes_shape", ("pyas_hist_axes", "pyas_select_axes"))):
+        for fn in fns:
+            start = re.search(rf"^int {fn}\(", capi, re.M)
+            assert start, fn
+            body = capi[start.end():]
+            assert f"{shape}(" in body[:re.search(r"^}", body, re.M).start()], fn
 
 
 def test_g1_reduced_positions_straddle_the_map():
