@@ -30,29 +30,11 @@
 // Byte order, mask rules and selection kind are run-time branches.
 #include <hip/hip_runtime.h>
 
-#include "pyas_kernels.hpp"   // ldg16, unpack16, unshuffle16, RadixCounter, decompose
-#include "pyas_records.hpp"   // the three combines over a record and its merge
-#include "pyas_comoments.hpp" // ComomMerge, CoAcc, com_wave_merge
+#include "pyas_records.hpp"     // the three combines over a record and its merge
+#include "pyas_comoments.hpp"   // ComomMerge, CoAcc
+#include "pyas_stat_walk.hpp"   // the tile share, the offset map, the record merges
 
 namespace pyas {
-
-// Wave merge, then the 4 waves in wave order; valid in thread 0.
-__device__ __forceinline__ void com_block_merge(pyas_comoments &p) {
-    __shared__ pyas_comoments s_w[kBlock / kWave];
-    com_wave_merge(p);
-    if ((threadIdx.x & (kWave - 1)) == 0) s_w[threadIdx.x / kWave] = p;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 1; k < kBlock / kWave; ++k) p = ComomMerge::merged(p, s_w[k]);
-    }
-}
-
-// one element, its byte order a run-time flag
-template <typename T, bool SHUF>
-__device__ __forceinline__ T com_load(const uint8_t *base, int64_t n, int64_t i, bool bsw) {
-    return bsw ? load_elem<T, SHUF, true>(base, n, i) : load_elem<T, SHUF, false>(base, n, i);
-}
 
 // RT: some side is byte-swapped (a run-time flag per side); else no branch
 template <typename T, bool RT>
@@ -73,12 +55,12 @@ __device__ __forceinline__ void com_run_elems(const uint8_t *bx, const uint8_t *
                                               bool bsx, bool bsy, CoAcc &acc, const MaskT<T> &mkx,
                                               const MaskT<T> &mky) {
     for (int64_t i = i0 + threadIdx.x; i < i1; i += kBlock) {
-        const T x = com_load<T, SX>(bx, n, i, bsx), y = com_load<T, SY>(by, n, i, bsy);
+        const T x = load_elem_bsw<T, SX>(bx, n, i, bsx), y = load_elem_bsw<T, SY>(by, n, i, bsy);
         acc.template add_n<1, M>(&x, &y, mkx, mky);
     }
 }
 
-// Both sides plain (the layout of mom_run_plain): the vector path needs the
+// Both sides plain (the layout of stat_run_plain): the vector path needs the
 // same head and tail on both sides, i.e. bases misaligned alike.
 template <typename T, int M, bool RT>
 __device__ void com_run_plain(const uint8_t *bx, const uint8_t *by, int64_t m0, int64_t m1, bool bsx, bool bsy,
@@ -96,12 +78,12 @@ __device__ void com_run_plain(const uint8_t *bx, const uint8_t *by, int64_t m0, 
     }
     const int64_t nhead = (a0 - b0) / ES, ntail = (b1 - a1) / ES;
     if (tid < nhead) {
-        const T x = com_load<T, false>(bx, 0, m0 + tid, bsx), y = com_load<T, false>(by, 0, m0 + tid, bsy);
+        const T x = load_elem_bsw<T, false>(bx, 0, m0 + tid, bsx), y = load_elem_bsw<T, false>(by, 0, m0 + tid, bsy);
         acc.template add_n<1, M>(&x, &y, mkx, mky);
     }
     if (tid < ntail) {
         const int64_t i = m1 - ntail + tid;
-        const T x = com_load<T, false>(bx, 0, i, bsx), y = com_load<T, false>(by, 0, i, bsy);
+        const T x = load_elem_bsw<T, false>(bx, 0, i, bsx), y = load_elem_bsw<T, false>(by, 0, i, bsy);
         acc.template add_n<1, M>(&x, &y, mkx, mky);
     }
     const uint4 *vx = reinterpret_cast<const uint4 *>(bx + a0);
@@ -175,7 +157,7 @@ __device__ __forceinline__ void com_group16(const uint8_t *base, int64_t n, int6
 }
 
 // A shuffled side (or both): elements [i0, i1) in groups of 16 as
-// mom_run_shuffled walks them; n = elements in the chunk.
+// stat_run_shuffled walks them; n = elements in the chunk.
 template <typename T, bool SX, bool SY, int M, bool RT>
 __device__ void com_run_groups(const uint8_t *bx, const uint8_t *by, int64_t n, int64_t i0, int64_t i1, bool bsx,
                                bool bsy, CoAcc &acc, const MaskT<T> &mkx, const MaskT<T> &mky) {
@@ -189,11 +171,11 @@ __device__ void com_run_groups(const uint8_t *bx, const uint8_t *by, int64_t n, 
         return;
     }
     if (tid < g0 - i0) {
-        const T x = com_load<T, SX>(bx, n, i0 + tid, bsx), y = com_load<T, SY>(by, n, i0 + tid, bsy);
+        const T x = load_elem_bsw<T, SX>(bx, n, i0 + tid, bsx), y = load_elem_bsw<T, SY>(by, n, i0 + tid, bsy);
         acc.template add_n<1, M>(&x, &y, mkx, mky);
     }
     if (tid < i1 - g1) {
-        const T x = com_load<T, SX>(bx, n, g1 + tid, bsx), y = com_load<T, SY>(by, n, g1 + tid, bsy);
+        const T x = load_elem_bsw<T, SX>(bx, n, g1 + tid, bsx), y = load_elem_bsw<T, SY>(by, n, g1 + tid, bsy);
         acc.template add_n<1, M>(&x, &y, mkx, mky);
     }
     const int64_t ng = (g1 - g0) / 16;
@@ -224,13 +206,8 @@ __device__ __forceinline__ void com_run(int mode, const uint8_t *bx, const uint8
     else com_run_m<T, SX, SY, kMaskAll, RT>(bx, by, n, i0, i1, bsx, bsy, acc, mkx, mky);
 }
 
-// the mask mode of one side, as k_moments_full picks it
-__device__ __forceinline__ int com_mode(bool masked, uint32_t f) {
-    return !masked || f == 0 ? 0 : (f & (PYAS_MASK_EQ0 | PYAS_MASK_EQ1)) ? kMaskAll : kMaskRange;
-}
-
 // ---------------------------------------------------------------------------
-// per-element walks (mom_walk / mom_walk_lds over two buffers)
+// per-element walks over two buffers
 // ---------------------------------------------------------------------------
 // How a walk loads and masks each side; the selection and geometry are x's.
 struct CoSide {
@@ -255,7 +232,7 @@ __device__ __forceinline__ void com_locate_y(const RadixCounter &rc, const MaskT
 template <typename T, int L>
 __device__ __forceinline__ T com_load_l(const uint8_t *base, int64_t n, int64_t i, bool shuf, bool bsw) {
     if constexpr (L == 2) return load_elem_rt<T>(base, n, i, shuf && sizeof(T) > 1, bsw);
-    else return com_load<T, L == 1>(base, n, i, bsw);
+    else return load_elem_bsw<T, L == 1>(base, n, i, bsw);
 }
 
 // Positions q0, q0 + stride, ... < n_pos over the dims in `dmask` (rc: the
@@ -361,17 +338,15 @@ __global__ __launch_bounds__(kBlock) void k_comoments_full(ComomentsArgs a) {
             if (!(s.start[d] == 0 && s.step[d] == 1 && cnt == r.shape[d])) inner_full = false;
         }
     }
-    // this tile's share of the selection: whole 16-element groups
-    const int64_t per = (((total + a.bpc - 1) / a.bpc) + 15) & ~(int64_t)15;
-    const int64_t e0 = t * per < total ? t * per : total;
-    const int64_t e1 = e0 + per < total ? e0 + per : total;
+    int64_t e0, e1;
+    tile_share(total, a.bpc, t, e0, e1);
     CoAcc acc;
     acc.init();
     if (e0 < e1) {
         if (contig) {
             // one mode for both sides: the wider of the two (a rule a side does
             // not have compares against its neutral thresholds)
-            const int mx = com_mode(a.masked_x, a.x.mask.flags), my = com_mode(a.masked_y, a.y.mask.flags);
+            const int mx = mask_mode(a.masked_x, a.x.mask.flags), my = mask_mode(a.masked_y, a.y.mask.flags);
             const int mode = (mx == kMaskAll || my == kMaskAll) ? kMaskAll : (mx | my);
             if (a.bswap_x || a.bswap_y)
                 com_run<T, SX, SY, true>(mode, bx, by, r.chunk_elems, m0 + e0, m0 + e1, a.bswap_x, a.bswap_y, acc,
@@ -388,12 +363,7 @@ __global__ __launch_bounds__(kBlock) void k_comoments_full(ComomentsArgs a) {
                                                 mkx, mky, acc);
         }
     }
-    pyas_comoments p = acc.finish();
-    com_block_merge(p);
-    if (threadIdx.x == 0) {
-        if (a.bpc > 1) a.tiles[blockIdx.x] = p;
-        else a.out[a.out_offsets ? a.out_offsets[c] : c] = p;
-    }
+    rec_store_full<ComomMerge>(acc, a, c);
 }
 
 // ---------------------------------------------------------------------------
@@ -420,19 +390,11 @@ __global__ __launch_bounds__(kBlock) void k_comoments_axes(ComomentsArgs a) {
             else n_keep *= s.cnt[d];
         }
     }
-    pyas_comoments *out = a.out + a.out_offsets[c];
     // the reduced positions' offsets, once per workgroup, when they fit
     __shared__ int32_t s_roff[kComRoff];
     const bool mapped = !(r.tab.on[0] || r.tab.on[1] || ytabs) && n_red <= kComRoff;   // uniform
-    if (mapped) {
-        for (int64_t q = threadIdx.x; q < n_red; q += kBlock) {
-            Decomp o{0, {0, 0}};
-            decompose(s, r.pool, r.cstride, r.tab, r.ndim, red, q, o);
-            s_roff[q] = (int32_t)o.mem;   // |offset| < chunk elements < 2^31
-        }
-        __syncthreads();
-    }
-    // the kept dims' part of output o: the element offset and x's table indices, y's table indices
+    if (mapped) stage_roff(r, s, red, n_red, s_roff);
+    pyas_comoments *out = a.out + a.out_offsets[c];
     auto kept_part = [&](int64_t o, Decomp &box, Decomp &boy) {
         box = Decomp{0, {0, 0}};
         boy = Decomp{0, {0, 0}};
@@ -474,7 +436,7 @@ __global__ __launch_bounds__(kBlock) void k_comoments_axes(ComomentsArgs a) {
                 }
             }
             pyas_comoments p = acc.finish();
-            com_wave_merge(p);
+            rec_wave_merge<pyas_comoments, ComomMerge>(p);
             if (lane == 0) out[o] = p;
         }
     }

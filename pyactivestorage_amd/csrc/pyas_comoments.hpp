@@ -24,6 +24,16 @@ struct ComomMerge {
         else if (a.count == 0) r = b;
         return r;
     }
+    static __device__ __forceinline__ pyas_comoments shfl_xor(const pyas_comoments &p, int m) {
+        pyas_comoments q;
+        q.count = pyas::shfl_xor(p.count, m);
+        q.mean_x = pyas::shfl_xor(p.mean_x, m);
+        q.mean_y = pyas::shfl_xor(p.mean_y, m);
+        q.m2_x = pyas::shfl_xor(p.m2_x, m);
+        q.m2_y = pyas::shfl_xor(p.m2_y, m);
+        q.cxy = pyas::shfl_xor(p.cxy, m);
+        return q;
+    }
 };
 
 struct CoAcc {
@@ -89,27 +99,5 @@ struct CoAcc {
         return p;
     }
 };
-
-__device__ __forceinline__ pyas_comoments com_shfl_xor(const pyas_comoments &p, int m) {
-    pyas_comoments q;
-    q.count = shfl_xor(p.count, m);
-    q.mean_x = shfl_xor(p.mean_x, m);
-    q.mean_y = shfl_xor(p.mean_y, m);
-    q.m2_x = shfl_xor(p.m2_x, m);
-    q.m2_y = shfl_xor(p.m2_y, m);
-    q.cxy = shfl_xor(p.cxy, m);
-    return q;
-}
-
-// Every lane of the wave participates; every lane ends with the wave's record
-// (pairs at distance 1, 2, 4, ...: the lower lane's side first).
-__device__ __forceinline__ void com_wave_merge(pyas_comoments &p) {
-    const int lane = threadIdx.x & (kWave - 1);
-#pragma unroll
-    for (int m = 1; m < kWave; m <<= 1) {
-        const pyas_comoments q = com_shfl_xor(p, m);
-        p = (lane & m) ? ComomMerge::merged(q, p) : ComomMerge::merged(p, q);
-    }
-}
 
 }  // namespace pyas

@@ -33,7 +33,7 @@
 // rules and selection kind are run-time branches.
 #include <hip/hip_runtime.h>
 
-#include "pyas_hist_walk.hpp"   // the runs, the per-element walk, hist_row, hist_flush
+#include "pyas_hist_walk.hpp"   // the counting accumulators, hist_row, hist_flush; the runs and the walk
 
 namespace pyas {
 
@@ -172,10 +172,8 @@ __global__ __launch_bounds__(kBlock) PYAS_HIST_WAVES(T) void k_hist_full(HistArg
                 if (!(s.start[d] == 0 && s.step[d] == 1 && cnt == r.shape[d])) inner_full = false;
             }
         }
-        // this tile's share of the selection: whole 16-element groups
-        const int64_t per = (((total + a.bpc - 1) / a.bpc) + 15) & ~(int64_t)15;
-        const int64_t e0 = t * per < total ? t * per : total;
-        const int64_t e1 = e0 + per < total ? e0 + per : total;
+        int64_t e0, e1;
+        tile_share(total, a.bpc, t, e0, e1);
         if (e0 >= e1) continue;
         const int64_t row = hist_row(a.out_offsets, a.out_index, c, 0);
         // a copy's count is at most `pending` (< 2^31 per pair): flush before it could wrap
@@ -186,16 +184,15 @@ __global__ __launch_bounds__(kBlock) PYAS_HIST_WAVES(T) void k_hist_full(HistArg
         cur_row = row;
         pending += (uint64_t)(e1 - e0);
         if (contig) {
-            const uint32_t f = r.mask.flags;
-            const int mode = !a.masked || f == 0 ? 0 : (f & (PYAS_MASK_EQ0 | PYAS_MASK_EQ1)) ? kMaskAll : kMaskRange;
-            if (a.bswap) hist_run<T, SHUF, true>(mode, base, r.chunk_elems, m0 + e0, m0 + e1, acc, mk);
-            else hist_run<T, SHUF, false>(mode, base, r.chunk_elems, m0 + e0, m0 + e1, acc, mk);
+            const int mode = mask_mode(a.masked, r.mask.flags);
+            if (a.bswap) stat_run<T, SHUF, true>(mode, base, r.chunk_elems, m0 + e0, m0 + e1, acc, mk);
+            else stat_run<T, SHUF, false>(mode, base, r.chunk_elems, m0 + e0, m0 + e1, acc, mk);
         } else if (e0 + threadIdx.x < e1) {
             const uint32_t all = (1u << r.ndim) - 1u;
             RadixCounter rc;
             rc.init(s, r.ndim, all, (uint64_t)(e0 + threadIdx.x), (uint64_t)kBlock);
             const Decomp zero{0, {0, 0}};
-            hist_walk<T, SHUF>(r, base, s, all, zero, rc, e0 + threadIdx.x, e1, kBlock, a.bswap, mk, acc);
+            stat_walk<T, SHUF>(r, base, s, all, zero, rc, e0 + threadIdx.x, e1, kBlock, a.bswap, mk, acc);
         }
     }
     if (pending) hist_flush(s_tab, slots, shift, a.table + cur_row * slots);
@@ -226,14 +223,8 @@ __global__ __launch_bounds__(kBlock) void k_hist_axes(HistArgs a) {
     MaskT<T> mk;
     mk.init(r.mask);
     const uint32_t red = a.axes, keep = ~a.axes & ((1u << r.ndim) - 1u);
-    int64_t n_keep = 1, n_red = 1;
-#pragma unroll
-    for (int d = 0; d < PYAS_MAX_DIMS; ++d) {
-        if (d < r.ndim) {
-            if ((red >> d) & 1u) n_red *= s.cnt[d];
-            else n_keep *= s.cnt[d];
-        }
-    }
+    int64_t n_keep, n_red;
+    axes_extents(s, r.ndim, red, n_keep, n_red);
     if (n_red <= 0) return;
     if (!a.row) {   // a lane per output
         for (int64_t o = b * kBlock + threadIdx.x; o < n_keep; o += a.bpc * kBlock) {
@@ -242,7 +233,7 @@ __global__ __launch_bounds__(kBlock) void k_hist_axes(HistArgs a) {
             RadixCounter rc;
             rc.init(s, r.ndim, red, 0, 1);
             const HistLane acc{bins, a.table + hist_row(a.out_offsets, a.out_index, c, o) * slots};
-            hist_walk<T, SHUF>(r, base, s, red, bo, rc, 0, n_red, 1, a.bswap, mk, acc);
+            stat_walk<T, SHUF>(r, base, s, red, bo, rc, 0, n_red, 1, a.bswap, mk, acc);
         }
     } else {        // `split` waves per output: wave part takes positions part * 64 + lane, + split * 64, ...
         constexpr int kWaves = kBlock / kWave;
@@ -256,7 +247,7 @@ __global__ __launch_bounds__(kBlock) void k_hist_axes(HistArgs a) {
                 RadixCounter rc;
                 rc.init(s, r.ndim, red, (uint64_t)q0, (uint64_t)(split * kWave));
                 const HistWave acc{bins, a.table + hist_row(a.out_offsets, a.out_index, c, o) * slots};
-                hist_walk<T, SHUF>(r, base, s, red, bo, rc, q0, n_red, split * kWave, a.bswap, mk, acc);
+                stat_walk<T, SHUF>(r, base, s, red, bo, rc, q0, n_red, split * kWave, a.bswap, mk, acc);
             }
         }
     }

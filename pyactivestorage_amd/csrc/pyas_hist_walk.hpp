@@ -1,13 +1,14 @@
-// pyas_hist_walk.hpp — the walkers shared by the counting kernels: binned
-// counts (pyas_hist.hip) and the digit counts of the radix select
-// (pyas_select.hip).  What an element adds to is the accumulator's business
-// (`Acc`): the runs call acc.add_n<N, M>(x, mk) (N values under mask mode M),
-// the per-element walk acc.add<N>(x, ok).
+// pyas_hist_walk.hpp — what the counting kernels share: binned counts
+// (pyas_hist.hip) and the digit counts of the radix select (pyas_select.hip).
+// The accumulators below go through the runs and the per-element walk of
+// pyas_stat_walk.hpp; which slot an element adds to is the business of their
+// rule `B`.  hist_row and hist_flush: the table row of an output, and the LDS
+// table's way into it.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
-#include "pyas_kernels.hpp"   // ldg16, unpack16, unshuffle16, RadixCounter, decompose, all_masked
+#include "pyas_stat_walk.hpp"   // the tile share, the runs, the per-element walk
 
 namespace pyas {
 
@@ -92,156 +93,6 @@ struct CountWave {
         }
     }
 };
-
-// ---------------------------------------------------------------------------
-// contiguous runs (the layout of mom_run_plain / mom_run_shuffled)
-// ---------------------------------------------------------------------------
-template <typename T, bool BSWAP, int M, typename Acc>
-__device__ __forceinline__ void hist_run_plain(const uint8_t *base, int64_t m0, int64_t m1, const Acc &acc, const MaskT<T> &mk) {
-    constexpr int ES = sizeof(T);
-    constexpr int N = 16 / ES;
-    const int tid = threadIdx.x;
-    const int64_t b0 = m0 * ES, b1 = m1 * ES;               // byte range in the chunk
-    const int64_t mis = (int64_t)((uintptr_t)base & 15);
-    const int64_t a0 = ((b0 + mis + 15) & ~(int64_t)15) - mis;  // first 16-B aligned byte
-    const int64_t a1 = ((b1 + mis) & ~(int64_t)15) - mis;
-    if (a0 >= a1) {
-        for (int64_t i = m0 + tid; i < m1; i += kBlock) {
-            const T v = load_plain<T, BSWAP>(base, i);
-            acc.template add_n<1, M>(&v, mk);
-        }
-        return;
-    }
-    const int64_t nhead = (a0 - b0) / ES, ntail = (b1 - a1) / ES;
-    if (tid < nhead) {
-        const T v = load_plain<T, BSWAP>(base, m0 + tid);
-        acc.template add_n<1, M>(&v, mk);
-    }
-    if (tid < ntail) {
-        const T v = load_plain<T, BSWAP>(base, m1 - ntail + tid);
-        acc.template add_n<1, M>(&v, mk);
-    }
-    const uint4 *v = reinterpret_cast<const uint4 *>(base + a0);
-    const int64_t nvec = (a1 - a0) / 16;
-    constexpr int U = 4;
-    constexpr int64_t STEP = (int64_t)U * kBlock;
-    const int64_t nsteps = nvec / STEP;
-    auto consume = [&](const uint4 *r) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            T x[N];
-            unpack16<T, BSWAP>(r[u], x);
-            acc.template add_n<N, M>(x, mk);
-        }
-    };
-    if (nsteps > 0) {
-        uint4 cur[U], nxt[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) cur[u] = ldg16(v + tid + u * kBlock);
-        for (int64_t s = 0; s + 1 < nsteps; ++s) {
-            // the next step's loads are in flight while this step is binned
-#pragma unroll
-            for (int u = 0; u < U; ++u) nxt[u] = ldg16(v + (s + 1) * STEP + tid + u * kBlock);
-            consume(cur);
-#pragma unroll
-            for (int u = 0; u < U; ++u) cur[u] = nxt[u];
-        }
-        consume(cur);
-    }
-    for (int64_t k = nsteps * STEP + tid; k < nvec; k += kBlock) {
-        T x[N];
-        unpack16<T, BSWAP>(ldg16(v + k), x);
-        acc.template add_n<N, M>(x, mk);
-    }
-}
-
-// Shuffled layout, chunk elements [i0, i1); n = elements in the chunk.
-template <typename T, bool BSWAP, int M, typename Acc>
-__device__ __forceinline__ void hist_run_shuffled(const uint8_t *base, int64_t n, int64_t i0, int64_t i1, const Acc &acc,
-                                  const MaskT<T> &mk) {
-    constexpr int ES = sizeof(T);
-    const int tid = threadIdx.x;
-    const bool vec_ok = (((uintptr_t)base & 15) == 0) && ((n & 15) == 0);
-    const int64_t g0 = (i0 + 15) & ~(int64_t)15, g1 = i1 & ~(int64_t)15;
-    if (!vec_ok || g0 >= g1) {
-        for (int64_t i = i0 + tid; i < i1; i += kBlock) {
-            const T v = load_shuffled<T, BSWAP>(base, n, i);
-            acc.template add_n<1, M>(&v, mk);
-        }
-        return;
-    }
-    if (tid < g0 - i0) {
-        const T v = load_shuffled<T, BSWAP>(base, n, i0 + tid);
-        acc.template add_n<1, M>(&v, mk);
-    }
-    if (tid < i1 - g1) {
-        const T v = load_shuffled<T, BSWAP>(base, n, g1 + tid);
-        acc.template add_n<1, M>(&v, mk);
-    }
-    const int64_t ng = (g1 - g0) / 16;
-    for (int64_t g = tid; g < ng; g += kBlock) {
-        const int64_t i = g0 + g * 16;
-        uint4 pl[ES];
-#pragma unroll
-        for (int b = 0; b < ES; ++b) pl[b] = ldg16(reinterpret_cast<const uint4 *>(base + (int64_t)b * n + i));
-        T x[16];
-        unshuffle16<T, BSWAP>(pl, x);
-        acc.template add_n<16, M>(x, mk);
-    }
-}
-
-template <typename T, bool SHUF, bool BSWAP, typename Acc>
-__device__ __forceinline__ void hist_run(int mode, const uint8_t *base, int64_t n, int64_t i0, int64_t i1,
-                                         const Acc &acc, const MaskT<T> &mk) {
-    if constexpr (SHUF && sizeof(T) > 1) {
-        if (mode == 0) hist_run_shuffled<T, BSWAP, 0>(base, n, i0, i1, acc, mk);
-        else if (mode == kMaskRange) hist_run_shuffled<T, BSWAP, kMaskRange>(base, n, i0, i1, acc, mk);
-        else hist_run_shuffled<T, BSWAP, kMaskAll>(base, n, i0, i1, acc, mk);
-    } else {
-        if (mode == 0) hist_run_plain<T, BSWAP, 0>(base, i0, i1, acc, mk);
-        else if (mode == kMaskRange) hist_run_plain<T, BSWAP, kMaskRange>(base, i0, i1, acc, mk);
-        else hist_run_plain<T, BSWAP, kMaskAll>(base, i0, i1, acc, mk);
-    }
-}
-
-template <typename T, bool SHUF>
-__device__ __forceinline__ T hist_load(const uint8_t *base, int64_t n, int64_t i, bool bsw) {
-    return bsw ? load_elem<T, SHUF, true>(base, n, i) : load_elem<T, SHUF, false>(base, n, i);
-}
-
-// Per-element walk of positions q0, q0 + stride, ... < n_pos over the dims in
-// `dmask` (rc: the radix counter at q0), 4 loads in flight.
-template <typename T, bool SHUF, typename Acc>
-__device__ __forceinline__ void hist_walk(const ReduceArgs &r, const uint8_t *base, const Sel &s, uint32_t dmask,
-                                          const Decomp &base_o, RadixCounter &rc, int64_t q0, int64_t n_pos,
-                                          int64_t stride, bool bsw, const MaskT<T> &mk, const Acc &acc) {
-    constexpr int U = 4;
-    int64_t q = q0;
-    for (; q + (U - 1) * stride < n_pos; q += U * stride) {
-        Decomp od[U];
-        T x[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            od[u] = base_o;
-            rc.locate(s, r.pool, r.cstride, r.tab, r.ndim, dmask, od[u]);
-            rc.advance();
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) x[u] = hist_load<T, SHUF>(base, r.chunk_elems, od[u].mem, bsw);
-        bool ok[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) ok[u] = !all_masked(mk, r.tab, od[u], x[u]);
-        acc.template add<U>(x, ok);
-    }
-    for (; q < n_pos; q += stride) {
-        Decomp od = base_o;
-        rc.locate(s, r.pool, r.cstride, r.tab, r.ndim, dmask, od);
-        rc.advance();
-        const T x = hist_load<T, SHUF>(base, r.chunk_elems, od.mem, bsw);
-        const bool ok = !all_masked(mk, r.tab, od, x);
-        acc.template add<1>(&x, &ok);
-    }
-}
 
 // the table row of output o (C order over the kept selected dims) of chunk c
 __device__ __forceinline__ int64_t hist_row(const int64_t *out_offsets, const int64_t *out_index, int64_t c, int64_t o) {

@@ -20,8 +20,8 @@
 // rules and selection kind are run-time branches (18 kernels each).
 #include <hip/hip_runtime.h>
 
-#include "pyas_kernels.hpp"   // ldg16, unpack16, unshuffle16, RadixCounter, decompose, all_masked
-#include "pyas_records.hpp"   // the tile / segment / grid combines
+#include "pyas_records.hpp"     // the tile / segment / grid combines
+#include "pyas_stat_walk.hpp"   // the runs, the offset map, the record merges
 
 namespace pyas {
 
@@ -39,6 +39,14 @@ struct MomMerge {
         if (b.count == 0) r = a;         // an empty side is skipped, not multiplied through
         else if (a.count == 0) r = b;
         return r;
+    }
+    static __device__ __forceinline__ pyas_moments shfl_xor(const pyas_moments &p, int m) {
+        pyas_moments q;
+        q.count = pyas::shfl_xor(p.count, m);
+        q.mean = pyas::shfl_xor(p.mean, m);
+        q.m2 = pyas::shfl_xor(p.m2, m);
+        q.reserved = 0;
+        return q;
     }
 };
 
@@ -89,149 +97,8 @@ struct MomAcc {
     }
 };
 
-// Every lane of the wave participates; every lane ends with the wave's record
-// (pairs at distance 1, 2, 4, ...: the lower lane's side first).
-__device__ __forceinline__ void mom_wave_merge(pyas_moments &p) {
-    const int lane = threadIdx.x & (kWave - 1);
-#pragma unroll
-    for (int m = 1; m < kWave; m <<= 1) {
-        pyas_moments q;
-        q.count = shfl_xor(p.count, m);
-        q.mean = shfl_xor(p.mean, m);
-        q.m2 = shfl_xor(p.m2, m);
-        q.reserved = 0;
-        p = (lane & m) ? MomMerge::merged(q, p) : MomMerge::merged(p, q);
-    }
-}
-
-// Wave merge, then the 4 waves in wave order; valid in thread 0.
-__device__ __forceinline__ void mom_block_merge(pyas_moments &p) {
-    __shared__ pyas_moments s_w[kBlock / kWave];
-    mom_wave_merge(p);
-    if ((threadIdx.x & (kWave - 1)) == 0) s_w[threadIdx.x / kWave] = p;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 1; k < kBlock / kWave; ++k) p = MomMerge::merged(p, s_w[k]);
-    }
-}
-
-// ---------------------------------------------------------------------------
-// contiguous runs (the layout of run_plain / run_shuffled in pyas_kernels.hpp)
-// ---------------------------------------------------------------------------
-template <typename T, bool BSWAP, int M>
-__device__ void mom_run_plain(const uint8_t *base, int64_t m0, int64_t m1, MomAcc &acc, const MaskT<T> &mk) {
-    constexpr int ES = sizeof(T);
-    constexpr int N = 16 / ES;
-    const int tid = threadIdx.x;
-    const int64_t b0 = m0 * ES, b1 = m1 * ES;               // byte range in the chunk
-    const int64_t mis = (int64_t)((uintptr_t)base & 15);
-    const int64_t a0 = ((b0 + mis + 15) & ~(int64_t)15) - mis;  // first 16-B aligned byte
-    const int64_t a1 = ((b1 + mis) & ~(int64_t)15) - mis;
-    if (a0 >= a1) {
-        for (int64_t i = m0 + tid; i < m1; i += kBlock) {
-            const T v = load_plain<T, BSWAP>(base, i);
-            acc.template add_n<1, M>(&v, mk);
-        }
-        return;
-    }
-    const int64_t nhead = (a0 - b0) / ES, ntail = (b1 - a1) / ES;
-    if (tid < nhead) {
-        const T v = load_plain<T, BSWAP>(base, m0 + tid);
-        acc.template add_n<1, M>(&v, mk);
-    }
-    if (tid < ntail) {
-        const T v = load_plain<T, BSWAP>(base, m1 - ntail + tid);
-        acc.template add_n<1, M>(&v, mk);
-    }
-    const uint4 *v = reinterpret_cast<const uint4 *>(base + a0);
-    const int64_t nvec = (a1 - a0) / 16;
-    constexpr int U = 4;
-    constexpr int64_t STEP = (int64_t)U * kBlock;
-    const int64_t nsteps = nvec / STEP;
-    auto consume = [&](const uint4 *r) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            T x[N];
-            unpack16<T, BSWAP>(r[u], x);
-            acc.template add_n<N, M>(x, mk);
-        }
-    };
-    if (nsteps > 0) {
-        uint4 cur[U], nxt[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) cur[u] = ldg16(v + tid + u * kBlock);
-        for (int64_t s = 0; s + 1 < nsteps; ++s) {
-            // the next step's loads are in flight while this step is reduced
-#pragma unroll
-            for (int u = 0; u < U; ++u) nxt[u] = ldg16(v + (s + 1) * STEP + tid + u * kBlock);
-            consume(cur);
-#pragma unroll
-            for (int u = 0; u < U; ++u) cur[u] = nxt[u];
-        }
-        consume(cur);
-    }
-    for (int64_t k = nsteps * STEP + tid; k < nvec; k += kBlock) {
-        T x[N];
-        unpack16<T, BSWAP>(ldg16(v + k), x);
-        acc.template add_n<N, M>(x, mk);
-    }
-}
-
-// Shuffled layout, chunk elements [i0, i1); n = elements in the chunk.
-template <typename T, bool BSWAP, int M>
-__device__ void mom_run_shuffled(const uint8_t *base, int64_t n, int64_t i0, int64_t i1, MomAcc &acc,
-                                 const MaskT<T> &mk) {
-    constexpr int ES = sizeof(T);
-    const int tid = threadIdx.x;
-    const bool vec_ok = (((uintptr_t)base & 15) == 0) && ((n & 15) == 0);
-    const int64_t g0 = (i0 + 15) & ~(int64_t)15, g1 = i1 & ~(int64_t)15;
-    if (!vec_ok || g0 >= g1) {
-        for (int64_t i = i0 + tid; i < i1; i += kBlock) {
-            const T v = load_shuffled<T, BSWAP>(base, n, i);
-            acc.template add_n<1, M>(&v, mk);
-        }
-        return;
-    }
-    if (tid < g0 - i0) {
-        const T v = load_shuffled<T, BSWAP>(base, n, i0 + tid);
-        acc.template add_n<1, M>(&v, mk);
-    }
-    if (tid < i1 - g1) {
-        const T v = load_shuffled<T, BSWAP>(base, n, g1 + tid);
-        acc.template add_n<1, M>(&v, mk);
-    }
-    const int64_t ng = (g1 - g0) / 16;
-    for (int64_t g = tid; g < ng; g += kBlock) {
-        const int64_t i = g0 + g * 16;
-        uint4 pl[ES];
-#pragma unroll
-        for (int b = 0; b < ES; ++b) pl[b] = ldg16(reinterpret_cast<const uint4 *>(base + (int64_t)b * n + i));
-        T x[16];
-        unshuffle16<T, BSWAP>(pl, x);
-        acc.template add_n<16, M>(x, mk);
-    }
-}
-
-template <typename T, bool SHUF, bool BSWAP>
-__device__ __forceinline__ void mom_run(int mode, const uint8_t *base, int64_t n, int64_t i0, int64_t i1,
-                                        MomAcc &acc, const MaskT<T> &mk) {
-    if constexpr (SHUF && sizeof(T) > 1) {
-        if (mode == 0) mom_run_shuffled<T, BSWAP, 0>(base, n, i0, i1, acc, mk);
-        else if (mode == kMaskRange) mom_run_shuffled<T, BSWAP, kMaskRange>(base, n, i0, i1, acc, mk);
-        else mom_run_shuffled<T, BSWAP, kMaskAll>(base, n, i0, i1, acc, mk);
-    } else {
-        if (mode == 0) mom_run_plain<T, BSWAP, 0>(base, i0, i1, acc, mk);
-        else if (mode == kMaskRange) mom_run_plain<T, BSWAP, kMaskRange>(base, i0, i1, acc, mk);
-        else mom_run_plain<T, BSWAP, kMaskAll>(base, i0, i1, acc, mk);
-    }
-}
-
-template <typename T, bool SHUF>
-__device__ __forceinline__ T mom_load(const uint8_t *base, int64_t n, int64_t i, bool bsw) {
-    return bsw ? load_elem<T, SHUF, true>(base, n, i) : load_elem<T, SHUF, false>(base, n, i);
-}
-
+// (pyas_stat_walk.hpp has this walk for the counting accumulators, which take the 4 elements in
+// one call; fed to MomAcc that way the kernels compile to other registers, so the copy stays.)
 // Per-element walk of positions q0, q0 + stride, ... < n_pos over the dims in
 // `dmask` (rc: the radix counter at q0), 4 loads in flight.
 template <typename T, bool SHUF>
@@ -250,7 +117,7 @@ __device__ __forceinline__ void mom_walk(const ReduceArgs &r, const uint8_t *bas
             rc.advance();
         }
 #pragma unroll
-        for (int u = 0; u < U; ++u) x[u] = mom_load<T, SHUF>(base, r.chunk_elems, od[u].mem, bsw);
+        for (int u = 0; u < U; ++u) x[u] = load_elem_bsw<T, SHUF>(base, r.chunk_elems, od[u].mem, bsw);
 #pragma unroll
         for (int u = 0; u < U; ++u) acc.add_one((double)x[u], !all_masked(mk, r.tab, od[u], x[u]));
     }
@@ -258,7 +125,7 @@ __device__ __forceinline__ void mom_walk(const ReduceArgs &r, const uint8_t *bas
         Decomp od = base_o;
         rc.locate(s, r.pool, r.cstride, r.tab, r.ndim, dmask, od);
         rc.advance();
-        const T x = mom_load<T, SHUF>(base, r.chunk_elems, od.mem, bsw);
+        const T x = load_elem_bsw<T, SHUF>(base, r.chunk_elems, od.mem, bsw);
         acc.add_one((double)x, !all_masked(mk, r.tab, od, x));
     }
 }
@@ -275,12 +142,12 @@ __device__ __forceinline__ void mom_walk_lds(const uint8_t *base, int64_t chunk_
     for (; q + (U - 1) * stride < n_pos; q += U * stride) {
         T x[U];
 #pragma unroll
-        for (int u = 0; u < U; ++u) x[u] = mom_load<T, SHUF>(base, chunk_elems, base_mem + roff[q + u * stride], bsw);
+        for (int u = 0; u < U; ++u) x[u] = load_elem_bsw<T, SHUF>(base, chunk_elems, base_mem + roff[q + u * stride], bsw);
 #pragma unroll
         for (int u = 0; u < U; ++u) acc.add_one((double)x[u], !mk.masked(x[u]));
     }
     for (; q < n_pos; q += stride) {
-        const T x = mom_load<T, SHUF>(base, chunk_elems, base_mem + roff[q], bsw);
+        const T x = load_elem_bsw<T, SHUF>(base, chunk_elems, base_mem + roff[q], bsw);
         acc.add_one((double)x, !mk.masked(x));
     }
 }
@@ -313,18 +180,15 @@ __global__ __launch_bounds__(kBlock) void k_moments_full(MomentsArgs a) {
             if (!(s.start[d] == 0 && s.step[d] == 1 && cnt == r.shape[d])) inner_full = false;
         }
     }
-    // this tile's share of the selection: whole 16-element groups
-    const int64_t per = (((total + a.bpc - 1) / a.bpc) + 15) & ~(int64_t)15;
-    const int64_t e0 = t * per < total ? t * per : total;
-    const int64_t e1 = e0 + per < total ? e0 + per : total;
+    int64_t e0, e1;
+    tile_share(total, a.bpc, t, e0, e1);
     MomAcc acc;
     acc.init();
     if (e0 < e1) {
         if (contig) {
-            const uint32_t f = r.mask.flags;
-            const int mode = !a.masked || f == 0 ? 0 : (f & (PYAS_MASK_EQ0 | PYAS_MASK_EQ1)) ? kMaskAll : kMaskRange;
-            if (a.bswap) mom_run<T, SHUF, true>(mode, base, r.chunk_elems, m0 + e0, m0 + e1, acc, mk);
-            else mom_run<T, SHUF, false>(mode, base, r.chunk_elems, m0 + e0, m0 + e1, acc, mk);
+            const int mode = mask_mode(a.masked, r.mask.flags);
+            if (a.bswap) stat_run<T, SHUF, true>(mode, base, r.chunk_elems, m0 + e0, m0 + e1, acc, mk);
+            else stat_run<T, SHUF, false>(mode, base, r.chunk_elems, m0 + e0, m0 + e1, acc, mk);
         } else if (e0 + threadIdx.x < e1) {
             const uint32_t all = (1u << r.ndim) - 1u;
             RadixCounter rc;
@@ -333,12 +197,7 @@ __global__ __launch_bounds__(kBlock) void k_moments_full(MomentsArgs a) {
             mom_walk<T, SHUF>(r, base, s, all, zero, rc, e0 + threadIdx.x, e1, kBlock, a.bswap, mk, acc);
         }
     }
-    pyas_moments p = acc.finish();
-    mom_block_merge(p);
-    if (threadIdx.x == 0) {
-        if (a.bpc > 1) a.tiles[blockIdx.x] = p;
-        else a.out[a.out_offsets ? a.out_offsets[c] : c] = p;
-    }
+    rec_store_full<MomMerge>(acc, a, c);
 }
 
 // ---------------------------------------------------------------------------
@@ -354,26 +213,13 @@ __global__ __launch_bounds__(kBlock) void k_moments_axes(MomentsArgs a) {
     MaskT<T> mk;
     mk.init(r.mask);
     const uint32_t red = a.axes, keep = ~a.axes & ((1u << r.ndim) - 1u);
-    int64_t n_keep = 1, n_red = 1;
-#pragma unroll
-    for (int d = 0; d < PYAS_MAX_DIMS; ++d) {
-        if (d < r.ndim) {
-            if ((red >> d) & 1u) n_red *= s.cnt[d];
-            else n_keep *= s.cnt[d];
-        }
-    }
-    pyas_moments *out = a.out + a.out_offsets[c];
+    int64_t n_keep, n_red;
+    axes_extents(s, r.ndim, red, n_keep, n_red);
     // the reduced positions' offsets, once per workgroup, when they fit
     __shared__ int32_t s_roff[kMomRoff];
     const bool mapped = !(r.tab.on[0] || r.tab.on[1]) && n_red <= kMomRoff;   // uniform
-    if (mapped) {
-        for (int64_t q = threadIdx.x; q < n_red; q += kBlock) {
-            Decomp o{0, {0, 0}};
-            decompose(s, r.pool, r.cstride, r.tab, r.ndim, red, q, o);
-            s_roff[q] = (int32_t)o.mem;   // |offset| < chunk elements < 2^31
-        }
-        __syncthreads();
-    }
+    if (mapped) stage_roff(r, s, red, n_red, s_roff);
+    pyas_moments *out = a.out + a.out_offsets[c];
     if (!a.row) {   // a lane per output
         for (int64_t o = b * kBlock + threadIdx.x; o < n_keep; o += a.bpc * kBlock) {
             MomAcc acc;
@@ -409,7 +255,7 @@ __global__ __launch_bounds__(kBlock) void k_moments_axes(MomentsArgs a) {
                 }
             }
             pyas_moments p = acc.finish();
-            mom_wave_merge(p);
+            rec_wave_merge<pyas_moments, MomMerge>(p);
             if (lane == 0) out[o] = p;
         }
     }

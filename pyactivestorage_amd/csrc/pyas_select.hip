@@ -25,7 +25,7 @@
 
 #include <type_traits>
 
-#include "pyas_hist_walk.hpp"   // the accumulators, the runs, the per-element walk, hist_row, hist_flush
+#include "pyas_hist_walk.hpp"   // the counting accumulators, hist_row, hist_flush; the runs and the walk
 
 namespace pyas {
 
@@ -133,10 +133,8 @@ __global__ __launch_bounds__(kBlock) PYAS_HIST_WAVES(T) void k_qsel_full(QselArg
                 if (!(s.start[d] == 0 && s.step[d] == 1 && cnt == r.shape[d])) inner_full = false;
             }
         }
-        // this tile's share of the selection: whole 16-element groups
-        const int64_t per = (((total + a.bpc - 1) / a.bpc) + 15) & ~(int64_t)15;
-        const int64_t e0 = t * per < total ? t * per : total;
-        const int64_t e1 = e0 + per < total ? e0 + per : total;
+        int64_t e0, e1;
+        tile_share(total, a.bpc, t, e0, e1);
         if (e0 >= e1) continue;
         // a copy's count is at most `pending` (< 2^31 per pair): flush before it could wrap
         if (pending && pending + (uint64_t)(e1 - e0) > 0xFFFFFFFFull) {
@@ -145,16 +143,15 @@ __global__ __launch_bounds__(kBlock) PYAS_HIST_WAVES(T) void k_qsel_full(QselArg
         }
         pending += (uint64_t)(e1 - e0);
         if (contig) {
-            const uint32_t f = r.mask.flags;
-            const int mode = !a.masked || f == 0 ? 0 : (f & (PYAS_MASK_EQ0 | PYAS_MASK_EQ1)) ? kMaskAll : kMaskRange;
-            if (a.bswap) hist_run<T, SHUF, true>(mode, base, r.chunk_elems, m0 + e0, m0 + e1, acc, mk);
-            else hist_run<T, SHUF, false>(mode, base, r.chunk_elems, m0 + e0, m0 + e1, acc, mk);
+            const int mode = mask_mode(a.masked, r.mask.flags);
+            if (a.bswap) stat_run<T, SHUF, true>(mode, base, r.chunk_elems, m0 + e0, m0 + e1, acc, mk);
+            else stat_run<T, SHUF, false>(mode, base, r.chunk_elems, m0 + e0, m0 + e1, acc, mk);
         } else if (e0 + threadIdx.x < e1) {
             const uint32_t all = (1u << r.ndim) - 1u;
             RadixCounter rc;
             rc.init(s, r.ndim, all, (uint64_t)(e0 + threadIdx.x), (uint64_t)kBlock);
             const Decomp zero{0, {0, 0}};
-            hist_walk<T, SHUF>(r, base, s, all, zero, rc, e0 + threadIdx.x, e1, kBlock, a.bswap, mk, acc);
+            stat_walk<T, SHUF>(r, base, s, all, zero, rc, e0 + threadIdx.x, e1, kBlock, a.bswap, mk, acc);
         }
     }
     if (pending) hist_flush(s_qsel, slots, shift, a.table);
@@ -175,14 +172,8 @@ __global__ __launch_bounds__(kBlock) void k_qsel_axes(QselArgs a) {
     MaskT<T> mk;
     mk.init(r.mask);
     const uint32_t red = a.axes, keep = ~a.axes & ((1u << r.ndim) - 1u);
-    int64_t n_keep = 1, n_red = 1;
-#pragma unroll
-    for (int d = 0; d < PYAS_MAX_DIMS; ++d) {
-        if (d < r.ndim) {
-            if ((red >> d) & 1u) n_red *= s.cnt[d];
-            else n_keep *= s.cnt[d];
-        }
-    }
+    int64_t n_keep, n_red;
+    axes_extents(s, r.ndim, red, n_keep, n_red);
     if (n_red <= 0) return;
     if (!a.row) {   // a lane per output
         for (int64_t o = b * kBlock + threadIdx.x; o < n_keep; o += a.bpc * kBlock) {
@@ -194,7 +185,7 @@ __global__ __launch_bounds__(kBlock) void k_qsel_axes(QselArgs a) {
             QselLane<T> acc;
             acc.b.init(a.shift, a.bits, a.prefix ? a.prefix[row] : 0ull);
             acc.row = a.table + row * slots;
-            hist_walk<T, SHUF>(r, base, s, red, bo, rc, 0, n_red, 1, a.bswap, mk, acc);
+            stat_walk<T, SHUF>(r, base, s, red, bo, rc, 0, n_red, 1, a.bswap, mk, acc);
         }
     } else {        // `split` waves per output: wave part takes positions part * 64 + lane, + split * 64, ...
         constexpr int kWaves = kBlock / kWave;
@@ -211,7 +202,7 @@ __global__ __launch_bounds__(kBlock) void k_qsel_axes(QselArgs a) {
                 QselWave<T> acc;
                 acc.b.init(a.shift, a.bits, a.prefix ? a.prefix[row] : 0ull);
                 acc.row = a.table + row * slots;
-                hist_walk<T, SHUF>(r, base, s, red, bo, rc, q0, n_red, split * kWave, a.bswap, mk, acc);
+                stat_walk<T, SHUF>(r, base, s, red, bo, rc, q0, n_red, split * kWave, a.bswap, mk, acc);
             }
         }
     }

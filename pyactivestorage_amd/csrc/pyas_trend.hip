@@ -40,8 +40,8 @@
 // k_trend_finalize : slope or intercept and the mask byte of n records.
 #include <hip/hip_runtime.h>
 
-#include "pyas_kernels.hpp"    // ldg16, unpack16, RadixCounter, decompose, all_masked
-#include "pyas_comoments.hpp"  // ComomMerge, CoAcc, com_wave_merge
+#include "pyas_comoments.hpp"   // ComomMerge, CoAcc
+#include "pyas_stat_walk.hpp"   // mask_mode, rec_wave_merge
 
 namespace pyas {
 
@@ -205,7 +205,7 @@ __global__ __launch_bounds__(kBlock) void k_trend_axes(TrendArgs a) {
                 }
             }
             pyas_comoments p = acc.finish();
-            com_wave_merge(p);
+            rec_wave_merge<pyas_comoments, ComomMerge>(p);
             if (lane == 0) out[o] = p;
         }
     }
@@ -414,8 +414,7 @@ __global__ __launch_bounds__(kBlock) PYAS_TREND_ATTR void k_trend_cols(TrendCols
     }
     MaskT<T> mk;
     mk.init(r.mask);
-    const uint32_t f = r.mask.flags;
-    const int mode = !a.masked || f == 0 ? 0 : (f & (PYAS_MASK_EQ0 | PYAS_MASK_EQ1)) ? kMaskAll : kMaskRange;
+    const int mode = mask_mode(a.masked, r.mask.flags);
     // 4-element loads: every row of the chunk starts at a multiple of 4 elements
     // (and so does every byte plane of a shuffled chunk)
     constexpr int64_t kAlign = (SHUF && ES > 1) ? 4 : (ES * V < 16 ? ES * V : 16);

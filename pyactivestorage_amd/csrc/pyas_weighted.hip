@@ -28,8 +28,8 @@
 // Both are templated on the dtype and shuffled-or-not only (18 kernels each).
 #include <hip/hip_runtime.h>
 
-#include "pyas_kernels.hpp"   // ldg16, unpack16, unshuffle16, RadixCounter, all_masked
-#include "pyas_records.hpp"   // the tile / segment / grid combines
+#include "pyas_records.hpp"     // the tile / segment / grid combines
+#include "pyas_stat_walk.hpp"   // the tile share, the record merges, load_elem_bsw
 
 namespace pyas {
 
@@ -41,6 +41,14 @@ struct WsumMerge {
         r.swx = a.swx + b.swx;
         r.reserved = 0;
         return r;
+    }
+    static __device__ __forceinline__ pyas_wsum shfl_xor(const pyas_wsum &p, int m) {
+        pyas_wsum q;
+        q.count = pyas::shfl_xor(p.count, m);
+        q.sw = pyas::shfl_xor(p.sw, m);
+        q.swx = pyas::shfl_xor(p.swx, m);
+        q.reserved = 0;
+        return q;
     }
 };
 
@@ -84,32 +92,6 @@ __device__ __forceinline__ void ws_mask_init(MaskT<T> &mk, const pyas_mask &m) {
     mk.hi1 = e1 ? TT<T>::from(m.eq_hi[1]) : small;
     mk.gt = (m.flags & PYAS_MASK_GT) ? TT<T>::from(m.gt) : big;
     mk.lt = (m.flags & PYAS_MASK_LT) ? TT<T>::from(m.lt) : small;
-}
-
-// Every lane of the wave participates; every lane ends with the wave's record
-// (pairs at distance 1, 2, 4, ...; an f64 add commutes exactly).
-__device__ __forceinline__ void ws_wave_merge(pyas_wsum &p) {
-#pragma unroll
-    for (int m = 1; m < kWave; m <<= 1) {
-        pyas_wsum q;
-        q.count = shfl_xor(p.count, m);
-        q.sw = shfl_xor(p.sw, m);
-        q.swx = shfl_xor(p.swx, m);
-        q.reserved = 0;
-        p = WsumMerge::merged(p, q);
-    }
-}
-
-// Wave merge, then the 4 waves in wave order; valid in thread 0.
-__device__ __forceinline__ void ws_block_merge(pyas_wsum &p) {
-    __shared__ pyas_wsum s_w[kBlock / kWave];
-    ws_wave_merge(p);
-    if ((threadIdx.x & (kWave - 1)) == 0) s_w[threadIdx.x / kWave] = p;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 1; k < kBlock / kWave; ++k) p = WsumMerge::merged(p, s_w[k]);
-    }
 }
 
 // ---------------------------------------------------------------------------
@@ -338,11 +320,6 @@ __device__ __forceinline__ void ws_run(int mode, const uint8_t *base, int64_t n,
 // ---------------------------------------------------------------------------
 // per-element walk: factors by dim, read from the pool
 // ---------------------------------------------------------------------------
-template <typename T, bool SHUF>
-__device__ __forceinline__ T ws_load(const uint8_t *base, int64_t n, int64_t i, bool bsw) {
-    return bsw ? load_elem<T, SHUF, true>(base, n, i) : load_elem<T, SHUF, false>(base, n, i);
-}
-
 // Positions q0, q0 + stride, ... < n_pos over the dims in `dmask` (rc: the
 // radix counter at q0), 4 loads in flight.  Dims outside dmask sit at chunk
 // index kli[d] (already part of base_o); org: the chunk's row of origin.
@@ -380,7 +357,7 @@ __device__ __forceinline__ void ws_walk(const ReduceArgs &r, const uint8_t *base
             rc.advance();
         }
 #pragma unroll
-        for (int u = 0; u < U; ++u) x[u] = ws_load<T, SHUF>(base, r.chunk_elems, od[u].mem, bsw);
+        for (int u = 0; u < U; ++u) x[u] = load_elem_bsw<T, SHUF>(base, r.chunk_elems, od[u].mem, bsw);
 #pragma unroll
         for (int u = 0; u < U; ++u) acc.add(x[u], w[u], !all_masked(mk, r.tab, od[u], x[u]));
     }
@@ -389,7 +366,7 @@ __device__ __forceinline__ void ws_walk(const ReduceArgs &r, const uint8_t *base
         double w;
         locate(od, w);
         rc.advance();
-        const T x = ws_load<T, SHUF>(base, r.chunk_elems, od.mem, bsw);
+        const T x = load_elem_bsw<T, SHUF>(base, r.chunk_elems, od.mem, bsw);
         acc.add(x, w, !all_masked(mk, r.tab, od, x));
     }
 }
@@ -426,12 +403,9 @@ __global__ __launch_bounds__(kBlock) void k_wsum_full(WsumArgs a) {
             if (!(s.start[d] == 0 && s.step[d] == 1 && cnt == r.shape[d])) inner_full = false;
         }
     }
-    // this tile's share of the selection: whole 16-element groups
-    const int64_t per = (((total + a.bpc - 1) / a.bpc) + 15) & ~(int64_t)15;
-    const int64_t e0 = t * per < total ? t * per : total;
-    const int64_t e1 = e0 + per < total ? e0 + per : total;
-    const uint32_t f = r.mask.flags;
-    const int mode = !a.masked || f == 0 ? 0 : (f & (PYAS_MASK_EQ0 | PYAS_MASK_EQ1)) ? kMaskAll : kMaskRange;
+    int64_t e0, e1;
+    tile_share(total, a.bpc, t, e0, e1);
+    const int mode = mask_mode(a.masked, r.mask.flags);
     __shared__ double s_wt[kWLds];
     WsAcc acc;
     acc.init();
@@ -459,12 +433,7 @@ __global__ __launch_bounds__(kBlock) void k_wsum_full(WsumArgs a) {
         ws_walk<T, SHUF>(r, base, s, all, zero, kli, a.wpool, org, rc, e0 + threadIdx.x, e1, kBlock, a.bswap, mk,
                          acc);
     }
-    pyas_wsum p = acc.finish();
-    ws_block_merge(p);
-    if (threadIdx.x == 0) {
-        if (a.bpc > 1) a.tiles[blockIdx.x] = p;
-        else a.out[a.out_offsets ? a.out_offsets[c] : c] = p;
-    }
+    rec_store_full<WsumMerge>(acc, a, c);
 }
 
 // ---------------------------------------------------------------------------
@@ -500,14 +469,8 @@ __global__ __launch_bounds__(kBlock) void k_wsum_axes(WsumArgs a) {
     MaskT<T> mk;
     ws_mask_init(mk, r.mask);
     const uint32_t red = a.axes, keep = ~a.axes & ((1u << r.ndim) - 1u);
-    int64_t n_keep = 1, n_red = 1;
-#pragma unroll
-    for (int d = 0; d < PYAS_MAX_DIMS; ++d) {
-        if (d < r.ndim) {
-            if ((red >> d) & 1u) n_red *= s.cnt[d];
-            else n_keep *= s.cnt[d];
-        }
-    }
+    int64_t n_keep, n_red;
+    axes_extents(s, r.ndim, red, n_keep, n_red);
     pyas_wsum *out = a.out + a.out_offsets[c];
     if (!a.row) {   // a lane per output
         for (int64_t o = b * kBlock + threadIdx.x; o < n_keep; o += a.bpc * kBlock) {
@@ -538,7 +501,7 @@ __global__ __launch_bounds__(kBlock) void k_wsum_axes(WsumArgs a) {
                 ws_walk<T, SHUF>(r, base, s, red, bo, kli, a.wpool, org, rc, lane, n_red, kWave, a.bswap, mk, acc);
             }
             pyas_wsum p = acc.finish();
-            ws_wave_merge(p);
+            rec_wave_merge<pyas_wsum, WsumMerge>(p);
             if (lane == 0) out[o] = p;
         }
     }
