@@ -13,6 +13,22 @@ if ROOT not in sys.path:
 SUM_RTOL = 1e-6   # BASELINE.json north star: <= 1e-6 relative for f32/f64 sum/mean
 
 
+def _tol(dt, ref_abs, n, abs_sum, against):
+    """SUM_RTOL of the reference; for f64 data never more than the derived
+    bound (tests/_compare.sum_bound): (2n + 2) u sum|x| against torch's own
+    f64 sum, twice (n + 2) u sum|x| between two kernel results, each within
+    that of the exact sum.  (At these sizes, n about 1e9 and more, the
+    worst-case bound is of the order of 1e-6 sum|x| itself: the rule that
+    bites at full size is the per-chunk one in tests/_fullsize_oracle.py.)"""
+    tol = SUM_RTOL * abs(ref_abs)
+    if dt.kind == "f" and dt.itemsize == 8:
+        from tests._compare import sum_bound
+        b = float(sum_bound(dt, n, abs_sum, "sum", ref="numpy")) if against == "reference" \
+            else 2 * float(sum_bound(dt, n, abs_sum, "sum"))
+        tol = min(tol, b)
+    return tol
+
+
 def _torch_reference(torch, buf, cfg, sels, missing, n_chunks):
     """count, f64 sum, min, max of the selected unmasked elements, on the
     device with plain torch ops (buf holds unshuffled chunk-major bytes)."""
@@ -24,7 +40,7 @@ def _torch_reference(torch, buf, cfg, sels, missing, n_chunks):
     batch = max(1, (256 << 20) // (celems * np.dtype(cfg["dtype"]).itemsize))
     idx = [torch.arange(c, device=dev).view([1] + [-1 if d == k else 1 for d in range(3)])
            for k, c in enumerate(chunks)]
-    count, total = 0, 0.0
+    count, total, abs_total = 0, 0.0, 0.0
     mn, mx = float("inf"), float("-inf")
     for b0 in range(0, n_chunks, batch):
         b1 = min(n_chunks, b0 + batch)
@@ -43,9 +59,10 @@ def _torch_reference(torch, buf, cfg, sels, missing, n_chunks):
                 ok &= (idx[k] >= s) & (idx[k] < e)
         count += int(ok.sum().item())
         total += float(torch.where(ok, v.double(), 0.0).sum().item())
+        abs_total += float(torch.where(ok, v.double().abs(), 0.0).sum().item())
         mn = min(mn, float(torch.where(ok, v, float("inf")).min().item()))
         mx = max(mx, float(torch.where(ok, v, float("-inf")).max().item()))
-    return count, total, mn, mx
+    return count, total, mn, mx, abs_total
 
 
 def _reduce(ctx, dt, cfg, buf, offsets, sels, missing, shuffled, stream):
@@ -80,11 +97,11 @@ def check(name):
                                            fill_frac=frac, seed=0, shuffle=False)
     torch.cuda.synchronize()
     got = _reduce(gpu, dt, cfg, plain, offsets, sels, missing, False, stream)
-    want_n, want_sum, want_min, want_max = _torch_reference(torch, plain, cfg, sels, missing, n_all)
+    want_n, want_sum, want_min, want_max, abs_sum = _torch_reference(torch, plain, cfg, sels, missing, n_all)
     assert int(got["count"]) == want_n
     assert want_n > 0
     assert float(got["min"]) == want_min and float(got["max"]) == want_max
-    assert abs(float(got["sum"]) - want_sum) <= SUM_RTOL * abs(want_sum)
+    assert abs(float(got["sum"]) - want_sum) <= _tol(dt, want_sum, want_n, abs_sum, "reference")
 
     # additivity over a split of the chunk list (two independent launches)
     h = n_all // 3
@@ -94,7 +111,7 @@ def check(name):
     assert min(float(p["min"]) for p in parts) == float(got["min"])
     assert max(float(p["max"]) for p in parts) == float(got["max"])
     psum = sum(float(p["sum"]) for p in parts)
-    assert abs(psum - float(got["sum"])) <= SUM_RTOL * abs(float(got["sum"]))
+    assert abs(psum - float(got["sum"])) <= _tol(dt, float(got["sum"]), want_n, abs_sum, "kernel")
 
     if cfg["shuffle"]:
         del plain
@@ -106,7 +123,7 @@ def check(name):
         # the un-shuffle changes which lane adds which element (sum order), not the set
         assert int(got_s["count"]) == int(got["count"])
         assert float(got_s["min"]) == float(got["min"]) and float(got_s["max"]) == float(got["max"])
-        assert abs(float(got_s["sum"]) - float(got["sum"])) <= SUM_RTOL * abs(float(got["sum"]))
+        assert abs(float(got_s["sum"]) - float(got["sum"])) <= _tol(dt, float(got["sum"]), want_n, abs_sum, "kernel")
         del shuf
     torch.cuda.empty_cache()
     print(f"fullsize {name} OK: count={int(got['count'])} sum={float(got['sum']):.9e} "

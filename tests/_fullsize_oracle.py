@@ -6,10 +6,14 @@ For each sampled chunk the HIP path's per-chunk partial (pyas_reduce_chunks
 over bench.py's generator, fill planting and selection table) must equal the
 oracle's ``storage.reduce_chunk`` (``storage.py:8-104``: un-shuffle, view,
 hyperslab, mask, then ``np.ma.count`` / ``np.ma.sum`` / ``np.ma.min`` /
-``np.ma.max``): count, min and max bit for bit, the f32/f64 sum within 1e-6
+``np.ma.max``): count, min and max bit for bit, the sum within 1e-6
 relative; and the combined total must equal the oracle's
 ``_from_storage`` combine over the same chunks (``active.py:575-630``):
-count, min, max exact, mean within 1e-6.
+count, min, max exact, mean within 1e-6.  The f64 config is also held to
+``tests/_compare.sum_bound``: each chunk's sum against the exact
+(``math.fsum``) sum of the oracle's masked selection, the combined mean
+against the exact sum over all sampled chunks (the chunks' exact sums added
+with ``math.fsum``: at most one more rounding each, counted in the bound).
 
 * C4: 64 chunks of 128^3 f32, byte-shuffled (es 4), _FillValue at 1 %,
   valid_min / valid_max (the chunks at coordinate 0 along dim 2: the
@@ -22,6 +26,7 @@ count, min, max exact, mean within 1e-6.
 Usage: python -m tests._fullsize_oracle {c4|c5}
 """
 import concurrent.futures
+import math
 import sys
 
 import numpy as np
@@ -33,6 +38,7 @@ def main(name):
     sys.path.insert(0, ".")
     import bench
     from oracle import storage_ref as ref
+    from tests._compare import assert_within, exact_reference, sum_bound
     from pyactivestorage_amd.batch import ReductionPlan
     from pyactivestorage_amd.device import get_context
     from pyactivestorage_amd.synthetic import chunk_major_device
@@ -63,6 +69,7 @@ def main(name):
     missing = (dt.type(bench.FILL), None, dt.type(bench.VMIN), None if unmasked else dt.type(bench.VMAX))
     filters = [ref.Shuffle(dt.itemsize)] if cfg["shuffle"] else None
     n_checked = n_partial = 0
+    worst = 0.0
     for ids in ranges:
         # each chunk generated on its own: a chunk's bytes (values and fill
         # planting) do not depend on the range it is generated in
@@ -96,6 +103,10 @@ def main(name):
                                                 (0, 1, 2), fn)
                 out[key] = tmp
                 out["n"] = n
+            if dt.itemsize == 8:
+                vals, _ = ref.reduce_chunk_bytes(raw, None, filters, missing, dt, chunks, "C", sel_of(c),
+                                                 (0, 1, 2), None)
+                out["exact"] = exact_reference(vals)
             return out
 
         with concurrent.futures.ThreadPoolExecutor(max_workers=16) as ex:
@@ -113,6 +124,11 @@ def main(name):
                 assert got.tobytes() == want.tobytes(), (name, ids[c], key, got, want)
             ws = float(np.asarray(np.ma.getdata(o["sum"])).reshape(-1)[0])
             assert abs(float(g["sum"]) - ws) <= 1e-6 * abs(ws), (name, ids[c], float(g["sum"]), ws)
+            if dt.itemsize == 8:
+                ex = o["exact"]
+                assert int(ex["n"][0]) == n
+                worst = max(worst, assert_within(np.array([float(g["sum"])]), ex["exact"],
+                                                 sum_bound(dt, ex["n"], ex["abs_sum"]), f"{name} chunk {ids[c]}"))
             n_checked += 1
         # the Active combine over these chunks (active.py:575-630)
         parts = {k: [(o[k], o["n"], (slice(c, c + 1), slice(0, 1), slice(0, 1))) for c, o in enumerate(ref_parts)]
@@ -123,6 +139,16 @@ def main(name):
         omean = float(np.asarray(np.ma.getdata(osum["sum"])).reshape(-1)[0]) / n
         gmean = float(np.asarray(total["sum"], dtype=dt)) / int(total["count"])
         assert abs(gmean - omean) <= 1e-6 * abs(omean), (name, gmean, omean)
+        if dt.itemsize == 8:
+            exs = [o["exact"] for o in ref_parts]
+            s_abs = math.fsum(float(e["abs_sum"][0]) for e in exs)
+            # fsum of the chunks' exactly rounded sums: u sum|x| over the chunks and one
+            # rounding more, with the kernel's (n - 1) u sum|x| inside sum_bound's n + 2
+            exact = math.fsum(float(e["exact"][0]) for e in exs)
+            bound = sum_bound(dt, n, s_abs, "mean", mean_abs=exact / n)
+            worst_mean = assert_within(np.array([gmean]), np.array([exact / n]), bound, f"{name} combined mean")
+            print(f"fullsize-oracle {name}{'u' if unmasked else ''} f64: worst chunk-sum error/bound "
+                  f"{worst:.3f}, combined mean over {n} values {worst_mean:.3f}")
         for key in ("min", "max"):
             want = np.asarray(np.ma.getdata(ref.combine_partials(parts[key], (hi - lo, 1, 1), dt, (0, 1, 2),
                                                                  key)), dtype=dt).reshape(-1)[0]

@@ -18,6 +18,7 @@ from oracle import storage_ref as ref
 from pyactivestorage_amd.active import Active
 from pyactivestorage_amd.variable import ChunkedVariable, get_missing_attributes
 from tests import _golden as G
+from tests._compare import assert_reduction_close
 
 pytestmark = pytest.mark.gpu
 
@@ -159,6 +160,9 @@ def test_active_axis_sweep(gpu, k):
             assert x.shape == r.shape, (axis, method)
             assert (x.mask == r.mask).all(), (axis, method)
             assert np.ma.allclose(x, r), (axis, method)
+            if method in ("mean", "sum"):     # tas is f64: the derived f64 bound as well
+                assert_reduction_close(x, sub, axis, sub.dtype, method, f"{index} {axis} {method}",
+                                       ok=~np.ma.getmaskarray(r).reshape(-1), extended=True)
             active.components = True
             active.method = method
             rn = np.ma.count(sub, axis=axis, keepdims=True)
@@ -170,3 +174,6 @@ def test_active_axis_sweep(gpu, k):
                 r = np.ma.sum(sub, axis=axis, keepdims=True)
             assert x[m].shape == r.shape and (x[m].mask == r.mask).all()
             assert np.ma.allclose(x[m], r), (axis, method)
+            if m == "sum":
+                assert_reduction_close(x[m], sub, axis, sub.dtype, "sum", f"{index} {axis} {method} components",
+                                       ok=~np.ma.getmaskarray(r).reshape(-1), extended=True)

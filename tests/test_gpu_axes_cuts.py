@@ -14,7 +14,8 @@ chunks, cut boxes at either end of one, two or every dim (the shapes of
 rule, and element- but not 16-byte-aligned chunk offsets; every chunk's
 partials (count, sum, min, max per output) are compared with
 ``oracle.storage_ref.reduce_chunk_bytes`` (``storage.py:95-100``): count,
-min and max exact, sums within 1e-6.  ``PYAS_AXES_CUTS=0`` (every cut chunk
+min and max exact, raw sums within ``tests/_compare.sum_bound`` of the exact
+sum.  ``PYAS_AXES_CUTS=0`` (every cut chunk
 on the generic walk) must give the same counts/min/max.
 Template: ``tests/unit/test_active_axis.py:30-78`` (hyperslabs x axis subsets).
 """
@@ -26,7 +27,7 @@ import pytest
 
 from oracle import storage_ref as ref
 from pyactivestorage_amd import _lib, engine, selection
-from tests._compare import shuffle_bytes
+from tests._compare import assert_sums_match_exact, assert_within, exact_reference, shuffle_bytes, sum_bound
 
 pytestmark = pytest.mark.gpu
 
@@ -129,7 +130,7 @@ def _check(dt, chunks, boxes, axes, miss, parts, what):
         acc = np.float64 if dt.kind == "f" else (np.int64 if dt.kind == "i" else np.uint64)
         wsum = np.ma.filled(vm.astype(acc), 0).sum(axis=axes, keepdims=True).reshape(-1)
         if dt.kind == "f":
-            np.testing.assert_allclose(p["sum"][ok], wsum[ok], rtol=1e-6, atol=1e-3, err_msg=w)
+            assert_sums_match_exact(p["sum"], vm, axes, dt, w, ok)
         else:
             np.testing.assert_array_equal(p["sum"][ok], wsum[ok], err_msg=w)
 
@@ -163,8 +164,16 @@ def test_cuts_off_agrees(gpu, axes, monkeypatch):
     on = _run(gpu, dt, shape, False, axes, miss, boxes, chunks)
     monkeypatch.setenv("PYAS_AXES_CUTS", "0")
     off = _run(gpu, dt, shape, False, axes, miss, boxes, chunks)
-    for a, b in zip(on, off):
+    for k, (a, b) in enumerate(zip(on, off)):
         assert a["count"].tobytes() == b["count"].tobytes()
         assert a["min"].tobytes() == b["min"].tobytes()
         assert a["max"].tobytes() == b["max"].tobytes()
         np.testing.assert_allclose(a["sum"], b["sum"], rtol=1e-6)
+        # and each path's raw sum is within sum_bound of the exact sum
+        vals, _ = ref.reduce_chunk_bytes(chunks[k].tobytes(), None, None, miss, dt.str, shape, "C", boxes[k],
+                                         axes, None)
+        ex = exact_reference(vals, axes)
+        bound = sum_bound(dt, ex["n"], ex["abs_sum"])
+        for side, p in (("cuts on", a), ("cuts off", b)):
+            assert_within(p["sum"], ex["exact"], bound, f"{side} chunk {k} axes={axes}",
+                          old=1e-6 * np.abs(ex["exact"]))

@@ -20,7 +20,7 @@ import pytest
 from oracle import storage_ref as ref
 from pyactivestorage_amd import _lib, engine
 from pyactivestorage_amd import storage as pas
-from tests._compare import assert_counts, assert_same, shuffle_bytes
+from tests._compare import assert_counts, assert_same, assert_sums_match_exact, shuffle_bytes
 
 pytestmark = pytest.mark.gpu
 
@@ -90,7 +90,7 @@ def test_dense_chunk_matches_oracle(gpu, case, shuf):
             with np.errstate(all="ignore"):
                 abs_sum = np.ma.sum(np.abs(np.ma.asarray(masked_sel).astype(np.float64)),
                                     axis=axis, keepdims=True)
-            assert_same(want, got, method.__name__, np.ma.filled(abs_sum, 0), what)
+            assert_same(want, got, method.__name__, np.ma.filled(abs_sum, 0), what, n=wn, data_dtype=dt)
             assert_counts(wn, gn, what)
 
 
@@ -164,7 +164,7 @@ def test_dense_batch_mixed_and_misaligned(gpu, dt, axes, shuf):
         acc = np.float64 if dt.kind == "f" else (np.int64 if dt.kind == "i" else np.uint64)
         wsum = np.ma.filled(vm.astype(acc), 0).sum(axis=axes, keepdims=True).reshape(-1)
         if dt.kind == "f":
-            np.testing.assert_allclose(part_k["sum"][ok], wsum[ok], rtol=1e-6, atol=1e-3, err_msg=what)
+            assert_sums_match_exact(part_k["sum"], vm, axes, dt, what, ok)
         else:
             np.testing.assert_array_equal(part_k["sum"][ok], wsum[ok], err_msg=what)
 
@@ -210,4 +210,9 @@ def test_vector_fill_on_whole_chunks(gpu, with_sels):
                                                             full, (0, 1, 2), None)[0])))
     assert int(tot["count"]) == want_n and want_n < 5 * chunks[0].size
     assert float(tot["min"]) == min(mins) and float(tot["max"]) == max(maxs)
-    np.testing.assert_allclose(float(tot["sum"]), want_sum, rtol=1e-6)
+    np.testing.assert_allclose(float(tot["sum"]), want_sum, rtol=1e-6)    # the oracle's own f32 chunk sums
+    # round_to_var=False: the total is the raw f64 sum of the f32 groups
+    sel_all = np.ma.stack([ref.reduce_chunk_bytes(a.tobytes(), None, None, miss, dt, shape, "C", full,
+                                                  (0, 1, 2), None)[0] for a in chunks])
+    assert_sums_match_exact(np.array([float(tot["sum"])]), sel_all, None, dt, "vector fill total",
+                            old_rtol=1e-6, old_atol=0.0)

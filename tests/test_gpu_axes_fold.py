@@ -18,7 +18,7 @@ from pyactivestorage_amd import active as active_mod
 from pyactivestorage_amd import engine
 from pyactivestorage_amd.active import Active
 from pyactivestorage_amd.variable import ChunkedVariable
-from tests._compare import shuffle_bytes
+from tests._compare import CAP_FOLD_MEAN, CAP_PARTIAL, assert_reduction_close, shuffle_bytes
 
 pytestmark = pytest.mark.gpu
 
@@ -145,7 +145,8 @@ def test_fold_matches_two_step(gpu, dtype, masked, case, monkeypatch):
     want = np.ma.masked_invalid(want)     # np.ma's out / n (active.py:630) masks NaN means
     np.testing.assert_array_equal(np.ma.getmaskarray(r1), np.ma.getmaskarray(want))
     ok = ~np.ma.getmaskarray(want)
-    np.testing.assert_allclose(np.ma.getdata(r1)[ok], np.ma.getdata(want)[ok], rtol=1e-5, atol=1e-4)
+    assert_reduction_close(r1, m, axis, dtype, "mean", f"{dtype} case {case} masked={masked}", ok=ok,
+                           old_rtol=CAP_FOLD_MEAN[0], old_atol=CAP_FOLD_MEAN[1])
 
 
 @pytest.mark.parametrize("dtype", ["<f4", ">f8", "<i4"])
@@ -176,8 +177,15 @@ def test_fold_shuffled_matches_two_step(gpu, dtype, case, monkeypatch):
             g_p, _, _ = _partials(plain, axis, index, True, monkeypatch, method)
             g_s, _, _ = _partials(var, axis, index, True, monkeypatch, method)
             _same_final(g_p, g_s, method)
-        # chunk sums are rounded to f32 (active.py:512) and these data cancel
-        np.testing.assert_allclose(fp["sum"], f1["sum"], rtol=1e-6, atol=1e-3)
+        # both against the exact sums: f4 chunk sums are rounded to f32
+        # (active.py:512) and these data cancel; f8 sums hold the f64 bound
+        sel = np.ma.masked_equal(data[index], var.attrs["_FillValue"][0])
+        for side, f in (("plain", fp), ("shuffled", f1)):
+            if np.dtype(dtype).kind == "f":
+                assert_reduction_close(f["sum"], sel, axis, dtype, "sum", f"{dtype} case 11 {side}",
+                                       old_rtol=CAP_PARTIAL[0], old_atol=CAP_PARTIAL[1])
+            else:
+                np.testing.assert_array_equal(f["sum"], np.ma.filled(sel, 0).sum(axis=axis).reshape(-1))
 
 
 def test_fold_refuses_long_rows(gpu, monkeypatch):
@@ -290,4 +298,5 @@ def test_combine_grid_wave_matches_thread(gpu, dtype, masked, case, monkeypatch)
     want = np.ma.masked_invalid(np.ma.mean(m.astype(np.float64), axis=axis, keepdims=True))
     np.testing.assert_array_equal(np.ma.getmaskarray(r_wave), np.ma.getmaskarray(want))
     ok = ~np.ma.getmaskarray(want)
-    np.testing.assert_allclose(np.ma.getdata(r_wave)[ok], np.ma.getdata(want)[ok], rtol=1e-5, atol=1e-4)
+    assert_reduction_close(r_wave, m, axis, dtype, "mean", f"{dtype} wave case {case} masked={masked}", ok=ok,
+                           old_rtol=CAP_FOLD_MEAN[0], old_atol=CAP_FOLD_MEAN[1])

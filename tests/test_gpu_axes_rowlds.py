@@ -44,5 +44,5 @@ def test_row_lds_matches_oracle(gpu, monkeypatch, lanes, dt):
                 what = f"lanes={lanes} {dt} {shape} miss={miss} axis={axis} {method.__name__}"
                 want, wn = ref.reduce_chunk_bytes(raw, None, None, miss, dt, shape, "C", sel, axis, method)
                 got, gn = pas.reduce_chunk_bytes(raw, None, None, miss, dt, shape, "C", sel, axis, method)
-                assert_same(want, got, method.__name__, np.ma.filled(abs_sum, 0), what)
+                assert_same(want, got, method.__name__, np.ma.filled(abs_sum, 0), what, n=wn, data_dtype=dt)
                 assert_counts(wn, gn, what)

@@ -17,7 +17,7 @@ import pytest
 
 from oracle import storage_ref as ref
 from pyactivestorage_amd import _lib, engine
-from tests._compare import shuffle_bytes
+from tests._compare import assert_sums_match_exact, shuffle_bytes
 
 pytestmark = pytest.mark.gpu
 
@@ -122,8 +122,7 @@ def test_stream_matches_oracle(gpu, monkeypatch, geom):
         for f, fn in (("min", np.ma.min), ("max", np.ma.max)):
             w = np.ma.getdata(fn(vm, axis=axes, keepdims=True)).reshape(-1)[ok]
             np.testing.assert_array_equal(got[k][f][ok].astype(np.float32), w, err_msg=f"chunk {k} {f}")
-        wsum = np.ma.filled(vm.astype(np.float64), 0).sum(axis=axes, keepdims=True).reshape(-1)
-        np.testing.assert_allclose(got[k]["sum"][ok], wsum[ok], rtol=1e-6, atol=1e-3)
+        assert_sums_match_exact(got[k]["sum"], vm, axes, dt, f"chunk {k}", ok)
 
 
 def test_auto_choice_at_size(gpu):

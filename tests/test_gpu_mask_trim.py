@@ -60,5 +60,5 @@ def test_trimmed_mask_matches_oracle(gpu, case):
                 with np.errstate(all="ignore"):
                     abs_sum = np.ma.sum(np.abs(np.ma.asarray(vals).astype(np.float64)), axis=axis,
                                         keepdims=True)
-                assert_same(want, got, method.__name__, np.ma.filled(abs_sum, 0), what)
+                assert_same(want, got, method.__name__, np.ma.filled(abs_sum, 0), what, n=wn, data_dtype=np_dt)
                 assert_counts(wn, gn, what)

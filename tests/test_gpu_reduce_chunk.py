@@ -126,7 +126,7 @@ def test_reduce_chunk_matches_oracle(gpu, case):
                 abs_sum = np.ma.sum(np.abs(np.ma.asarray(masked_sel).astype(np.float64)),
                                     axis=axis, keepdims=True)
             kind = method.__name__.replace("amin", "min").replace("amax", "max")
-            assert_same(want, got, kind, np.ma.filled(abs_sum, 0), what)
+            assert_same(want, got, kind, np.ma.filled(abs_sum, 0), what, n=wn, data_dtype=dt)
             assert_counts(wn, gn, what)
 
 

@@ -9,20 +9,27 @@ import pytest
 
 from pyactivestorage_amd.active import Active, release_resident
 from tests import _dist_active as D
-from tests.test_gpu_active import variable
+from tests._compare import assert_reduction_close, assert_within
+from tests.test_gpu_active import full_array, variable
 
 pytestmark = pytest.mark.gpu
 
 
-def _same(a, b, what, method="min"):
+def _same(a, b, what, method="min", sel=None, axis=None):
     """Bit-exact, except sums/means of shuffled variables: the resident
     store keeps chunks un-shuffled, and the fresh path's fused un-shuffle
-    adds the elements in another order (1e-6 relative, the north star's
-    tolerance; counts, masks, min and max stay exact)."""
+    adds the elements in another order.  test1.nc is float64: each side is
+    within sum_bound of the exact reduction of the oracle's masked selection
+    ``sel`` (and the two within 1e-6 relative of each other, as before);
+    counts, masks, min and max stay exact."""
     assert type(a) is type(b) and np.shape(a) == np.shape(b), what
     np.testing.assert_array_equal(np.ma.getmaskarray(a), np.ma.getmaskarray(b), err_msg=what)
     if method in ("sum", "mean"):
-        np.testing.assert_allclose(np.ma.getdata(a), np.ma.getdata(b), rtol=1e-6, err_msg=what)
+        assert sel.dtype == np.float64
+        ok = ~np.ma.getmaskarray(a).reshape(-1)
+        for side, r in (("resident", a), ("fresh", b)):
+            assert_reduction_close(r, sel, axis, sel.dtype, method, f"{what} {side}", ok=ok)
+        assert_within(np.ma.getdata(a), np.ma.getdata(b), 1e-6 * np.abs(np.ma.getdata(b)), what)
     else:
         np.testing.assert_array_equal(np.ma.getdata(a), np.ma.getdata(b), err_msg=what)
 
@@ -37,6 +44,7 @@ def _query(var, method, axis, index, resident):
 @pytest.mark.parametrize("make", ["synthetic", "test1.nc:tas"])
 def test_resident_matches_fresh(gpu, make):
     var = D.make_variable() if make == "synthetic" else variable(make)
+    full = None if make == "synthetic" else full_array(make)
     nd = len(var.shape)
     half = tuple(slice(0, max(1, n // 2)) for n in var.shape)
     other = tuple(slice(n // 3, n) for n in var.shape)
@@ -47,13 +55,14 @@ def test_resident_matches_fresh(gpu, make):
         for k, (method, axis, index) in enumerate(queries):
             want, _ = _query(var, method, axis, index, False)
             got, read = _query(var, method, axis, index, True)
-            _same(got, want, f"{make} query {k}", method if make != "synthetic" else "exact")
+            _same(got, want, f"{make} query {k}", method if make != "synthetic" else "exact",
+                  None if full is None else full[index], axis)
             seen += read
         # every chunk is now resident: a repeat reads nothing
         got, read = _query(var, "mean", None, (slice(None),) * nd, True)
         assert read == 0
         want, full_read = _query(var, "mean", None, (slice(None),) * nd, False)
-        _same(got, want, f"{make} repeat", "mean" if make != "synthetic" else "exact")
+        _same(got, want, f"{make} repeat", "mean" if make != "synthetic" else "exact", full, None)
         assert 0 < seen <= full_read
     finally:
         release_resident(var)

@@ -12,7 +12,7 @@ groups over the byte planes), and span-granular tiling (several tiles per
 chunk, fewer spans than tiles).  Every case here compares each chunk's
 partial (sum, count, min, max) of a ``ReductionPlan`` batch with
 ``oracle.storage_ref.reduce_chunk_bytes`` (``storage.py:95-100``) on the
-same bytes: count/min/max exact, sums within the north-star 1e-6.
+same bytes: count/min/max exact, raw sums within tests/_compare.sum_bound.
 """
 import zlib
 
@@ -23,7 +23,7 @@ from oracle import storage_ref as ref
 from pyactivestorage_amd import selection
 from pyactivestorage_amd.batch import ReductionPlan
 from pyactivestorage_amd.device import DeviceBuffer
-from tests._compare import shuffle_bytes
+from tests._compare import assert_within, exact_reference, shuffle_bytes, sum_bound
 
 pytestmark = pytest.mark.gpu
 
@@ -148,8 +148,12 @@ def test_spans_match_oracle(gpu, monkeypatch, dt, shape, shuffle, masked, tile_b
         assert parts[c]["max"] == np.asarray(mx).reshape(-1)[0], f"{what}: max {parts[c]['max']} != {mx}"
         want = np.asarray(np.ma.getdata(s_w)).reshape(-1)[0]
         if dt.kind == "f":
+            # round_to_var=False: the raw f64 sum, against the exact sum of the
+            # masked selection (and never more than the earlier rule)
             sel_abs = np.abs(data[c][sels[c]].astype(np.float64)).sum()
-            assert abs(float(parts[c]["sum"]) - float(want)) <= max(1e-6 * abs(float(want)), 4e-7 * sel_abs), \
-                f"{what}: sum {parts[c]['sum']} != {want}"
+            vals, _ = ref.reduce_chunk_bytes(raws[c], None, None, missing, dt.str, shape, "C", sels[c], axis, None)
+            ex = exact_reference(vals)
+            assert_within(np.array([float(parts[c]["sum"])]), ex["exact"], sum_bound(dt, ex["n"], ex["abs_sum"]),
+                          f"{what}: sum", old=np.array([max(1e-6 * abs(float(want)), 4e-7 * sel_abs)]))
         else:
             assert int(parts[c]["sum"]) == int(want), f"{what}: sum {parts[c]['sum']} != {want}"
