@@ -646,6 +646,69 @@ enum { PYAS_TREND_SLOPE = 0, PYAS_TREND_INTERCEPT = 1 };
 int pyas_trend_finalize(pyas_ctx *ctx, const pyas_comoments *in, int64_t n, int32_t what,
                         double *value, uint8_t *masked, void *stream);
 
+/* ---- per-label second moments (Active.grouped) -------------------------------
+ * The pyas_moments record, one per (output, group): an element whose global
+ * index along one reduced dim is i belongs to group labels[i] >= 0, or to no
+ * group (labels[i] < 0).  The host turns the labels into the tables below;
+ * like the selection table they are trusted (the host builds and checks
+ * them).  Lanes accumulate exactly as for pyas_moments_axes. */
+
+/* The reduced rows of a unit-step box query, for pyas_group_cols.  A row is
+ * one position of the reduced (leading) dims' selection: its chunk layer (the
+ * C-order position of its chunk over the reduced dims' chunk coordinates), its
+ * element offset inside the chunk (sum over the reduced dims of the index
+ * inside the chunk times the chunk's element stride) and its label.  Only
+ * rows with a label >= 0 are listed, sorted by label (stably: in increasing
+ * global order inside a label), so every group is one run.  Every column of
+ * chunks walks the same list. */
+typedef struct {
+    const int32_t *layer;    /* device [n_rows] */
+    const int32_t *offset;   /* device [n_rows] */
+    const int32_t *label;    /* device [n_rows]: non-decreasing, in [0, n_groups) */
+    int64_t n_rows;          /* 0: every record is the zero record (the pointers may be NULL) */
+    int32_t n_groups;
+} pyas_group_rows;
+#define PYAS_GROUP_ROWS 1024 /* rows of the list a workgroup of pyas_group_cols stages per pass */
+
+/* The dense path of a box query, in ONE launch: out[g * n_out + o] (device;
+ * o in C order over grid->out_extent, n_out = their product) receives the
+ * finished record of final output o over the rows of group g, for every g in
+ * [0, n_groups): the zero record where the group has no row.  The kernel
+ * writes every one of these records, so `out` needs no initialisation.  The
+ * caller's promises, the geometries taken and PYAS_ENOTSUP (nothing launched;
+ * the caller takes pyas_group_axes) are those of pyas_trend_cols; rows->n_rows
+ * < 0 or n_groups < 0 is PYAS_EINVAL, n_groups == 0 launches nothing.  A lane
+ * owns 4 consecutive outputs along the innermost dim and walks the list in
+ * order; at a change of label it stores its 4 records and starts again, so a
+ * record is the lane's own sums over all chunk layers (nothing is merged) and
+ * results are bit-identical from run to run.  Rows that are not listed are
+ * never read. */
+int pyas_group_cols(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask,
+                    const pyas_group_rows *rows, const pyas_grid *grid, pyas_moments *out,
+                    void *stream);
+
+/* The groups of each chunk, for pyas_group_axes (CSR): chunk c has the local
+ * groups chunk_start[c] .. chunk_start[c+1]; local group j holds the positions
+ * pos[ptr[j] .. ptr[j+1]) among the chunk's SELECTED indices along chunk dim
+ * `dim` (position k is the k-th entry of the dim's selection in the chunk, the
+ * index the selection table and the mask tables' strides see), increasing. */
+typedef struct {
+    const int32_t *chunk_start;   /* device [n_chunks + 1] */
+    const int32_t *ptr;           /* device [n_local_groups + 1] */
+    const int32_t *pos;           /* device */
+    int32_t dim;                  /* must be in the reduced dims */
+} pyas_group_lists;
+
+/* pyas_moments_axes with one record per (chunk output, chunk-local group):
+ * out[out_offsets[c] + j * n_keep + o] receives the record of output o (C
+ * order over the n_keep kept selected positions of chunk c) over local group
+ * j of chunk c (j from 0).  Errors as pyas_trend_axes (lists for coord; out_offsets
+ * is always needed).  pyas_moments_combine_segments merges the records.  A
+ * per-element walk for any selection and mask: it has no speed target. */
+int pyas_group_axes(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask,
+                    const pyas_group_lists *lists, uint32_t axes_mask, const int64_t *out_offsets,
+                    pyas_moments *out, void *stream);
+
 /* ---- weighted sums (Active.mean / Active.sum with weights=) -----------------
  * Partial record of a weighted mean over a set of elements (32 bytes):
  * count unmasked elements; sw = sum w; swx = sum w x  (f64).  The all-zero

@@ -68,6 +68,21 @@ class Coord(ctypes.Structure):
 TREND_SLOPE, TREND_INTERCEPT = 0, 1
 
 
+class GroupRows(ctypes.Structure):
+    """pyas_group_rows: the sorted reduced rows of a box query (device pointers) and the group count."""
+    _fields_ = [("layer", ctypes.c_void_p), ("offset", ctypes.c_void_p), ("label", ctypes.c_void_p),
+                ("n_rows", ctypes.c_int64), ("n_groups", ctypes.c_int32)]
+
+
+class GroupLists(ctypes.Structure):
+    """pyas_group_lists: each chunk's groups as lists of positions among its selected indices (device pointers)."""
+    _fields_ = [("chunk_start", ctypes.c_void_p), ("ptr", ctypes.c_void_p), ("pos", ctypes.c_void_p),
+                ("dim", ctypes.c_int32)]
+
+
+GROUP_ROWS = 1024   # pyas.h PYAS_GROUP_ROWS: rows of the sorted list pyas_group_cols stages per pass
+
+
 class Hist(ctypes.Structure):
     """pyas_hist: device edges (n_bins + 1), PYAS_HIST_* flags and the uniform guess (lo, scale)."""
     _fields_ = [("edges", ctypes.c_void_p), ("n_bins", ctypes.c_int32), ("flags", ctypes.c_uint32),
@@ -263,6 +278,10 @@ SIGNATURES = {
     "pyas_trend_cols": [_vp, ctypes.POINTER(Batch), ctypes.POINTER(Mask), ctypes.POINTER(Coord),
                         ctypes.POINTER(Grid), _vp, _vp],
     "pyas_trend_finalize": [_vp, _vp, _i64, _i32, _vp, _vp, _vp],
+    "pyas_group_cols": [_vp, ctypes.POINTER(Batch), ctypes.POINTER(Mask), ctypes.POINTER(GroupRows),
+                        ctypes.POINTER(Grid), _vp, _vp],
+    "pyas_group_axes": [_vp, ctypes.POINTER(Batch), ctypes.POINTER(Mask), ctypes.POINTER(GroupLists), _u32, _vp, _vp,
+                        _vp],
     "pyas_wsum_axes": [_vp, ctypes.POINTER(Batch), ctypes.POINTER(Mask), ctypes.POINTER(Weights), _u32, _vp, _vp,
                        _vp],
     "pyas_wsum_combine_segments": [_vp, _vp, _vp, _vp, _i64, _vp, _vp],

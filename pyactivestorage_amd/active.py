@@ -43,6 +43,7 @@ both variables' chunks (``pyas_comoments_axes``) merged like the var records
 from __future__ import annotations
 
 import concurrent.futures
+import itertools
 import os
 import threading
 from types import SimpleNamespace
@@ -51,7 +52,7 @@ import warnings
 
 import numpy as np
 
-from . import _lib, comoments, engine, histogram, moments, quantile, selection, trend, weighted, zerosign
+from . import _lib, comoments, engine, grouped, histogram, moments, quantile, selection, trend, weighted, zerosign
 from .batch import ReductionPlan, _all_full
 from .device import DeviceBuffer, get_context
 from .dtypes import native, sum_dtype
@@ -408,6 +409,8 @@ class Active:
         self._co = None                 # cov / corr: the second variable's Active of the next query
         self._trend = None              # trend: {"along": dim >= 0, "coord": float64 vector} of the next query
         self._trend_path = None         # the last trend query: "cols" (dense column kernel) or "walk"
+        self._grouped = None            # grouped: {"stat", "along", "labels", "n_groups"} of the next query
+        self._grouped_path = None       # the last grouped query: "cols" (dense column kernel) or "walk"
         self._select_stats = None       # the last quantile query: its digit width, count launches and chains
         self._max_threads = int(max_threads)
         self.device = device
@@ -453,6 +456,15 @@ class Active:
         self._quant = None
         self._co = None
         self._trend = None
+        self._grouped = None
+
+    @property
+    def grouped_path(self):
+        """Which kernel the last :meth:`grouped` query ran: ``"cols"`` (the
+        dense column walk, pyas_group_cols) or ``"walk"`` (the per-element
+        walk, pyas_group_axes); None before the first one and after a query
+        that reached no kernel (an empty selection, no group)."""
+        return self._grouped_path
 
     @property
     def trend_path(self):
@@ -604,6 +616,43 @@ class Active:
             self._axis = axis
         return self
 
+    def grouped(self, stat, along, labels, axis=None, ddof=0, n_groups=None):
+        """One statistic per label along a reduced dimension, in one pass on
+        the device: ``stat`` (``"mean"``, ``"var"``, ``"std"`` or ``"count"``)
+        of the selected unmasked elements whose global index ``i`` along
+        dimension ``along`` has ``labels[i] == g``, for every group ``g`` in
+        ``range(G)``: a monthly climatology with ``labels`` the month of each
+        time step.  ``along``: an int in ``[-ndim, ndim)`` that must be among
+        the reduced axes; ``labels``: 1-D, ``shape[along]`` integers, a
+        negative one putting its index in no group (on the dense path such
+        rows are not read); ``n_groups``: ``G``, None meaning
+        ``max(labels) + 1`` (0 when every label is negative); ``ddof``: as for
+        :meth:`var` (``mean`` and ``count`` ignore it).  The query returns an
+        array of ``final_shape`` with ``G`` in place of the 1 along ``along``:
+        for ``mean``, ``var`` and ``std`` a float64 masked array (``mean``
+        masked where the group counts no element, ``var`` / ``std`` where
+        ``count - ddof <= 0``; NaN where a counted value is NaN or infinite),
+        for ``count`` an int64 ``ndarray``.  An element's value is its float64
+        conversion, as for :meth:`var`.  With ``components`` a dict of
+        ``mean``, ``m2`` and ``n`` as :meth:`var` returns them, so
+        ``moments.merge`` combines the components of disjoint selections.  A
+        unit-step box query whose reduced axes are a leading prefix of the dims
+        (``along=0, axis=(0,)``) runs the dense column kernel
+        (pyas_group_cols), anything else the per-element walk
+        (pyas_group_axes): see :attr:`grouped_path`.  The settings hold for
+        one query."""
+        if stat not in grouped.STATS:
+            raise ValueError(f"grouped: stat must be one of {grouped.STATS}. Got {stat!r}")
+        ndim = self.ds.ndim
+        if isinstance(along, (bool, np.bool_)) or not isinstance(along, (int, np.integer)) \
+                or not -ndim <= along < ndim:
+            raise ValueError(f"grouped: along={along!r} is out of range for {ndim} dimensions")
+        d = int(along) % ndim
+        lab, n_g = grouped.check_labels(labels, self.ds.shape[d], n_groups)
+        self._set_moments("grouped", axis, ddof)
+        self._grouped = {"stat": stat, "along": d, "labels": lab, "n_groups": n_g}
+        return self
+
     def histogram(self, bins=10, range=None, axis=None):   # noqa: A002 - NumPy's argument name
         """Binned counts of the unmasked elements, one pass on the device
         (pyas_hist_axes).  Each element converts to float64 as
@@ -699,6 +748,7 @@ class Active:
             self._quant = None           # and a quantile's q and method
             self._co = None              # and a cov / corr's second variable
             self._trend = None           # and a trend's coordinate
+            self._grouped = None         # and a grouped query's labels
             for store in held:
                 _unhold(store)
             self._held.stores = []
@@ -725,6 +775,9 @@ class Active:
         tr = self._method == "trend"
         if tr and self.group is not None:
             raise NotImplementedError("trend with group=…: co-moments are reduced on one GPU only")
+        gr = self._method == "grouped"
+        if gr and self.group is not None:
+            raise NotImplementedError("grouped with group=…: second moments are reduced on one GPU only")
         if self._axis is None:
             self._axis = tuple(range(ds.ndim))
         elif isinstance(self._axis, int):
@@ -732,11 +785,14 @@ class Active:
         if tr and self._trend["along"] not in self._norm_axes():
             raise ValueError(f"trend: along={self._trend['along']} is not among the reduced axes "
                              f"{self._norm_axes()}: the coordinate would be constant per output")
+        if gr and self._grouped["along"] not in self._norm_axes():
+            raise ValueError(f"grouped: along={self._grouped['along']} is not among the reduced axes "
+                             f"{self._norm_axes()}: every output would hold one label")
         cache_key = None
-        # (var / std, weighted, histogram, quantile, cov / corr and trend queries bypass the plan cache: its plans
-        # replay pyas_partial launches)
+        # (var / std, weighted, histogram, quantile, cov / corr, trend and grouped queries bypass the plan cache: its
+        # plans replay pyas_partial launches)
         if self.resident and self.group is None and self._method is not None and not second and not has_w \
-                and not hist and not quant and not co and not tr:
+                and not hist and not quant and not co and not tr and not gr:
             ikey = _index_key(index)
             if ikey is not None:
                 cache_key = (ikey, self._norm_axes(), _missing_key(self.missing))
@@ -766,6 +822,8 @@ class Active:
             return self._reduce_comoments(indexer, compressor, filters, self._norm_axes())
         if tr:
             return self._reduce_trend(indexer, compressor, filters, self._norm_axes())
+        if gr:
+            return self._reduce_grouped(indexer, compressor, filters, self._norm_axes())
         return self._reduce(indexer, compressor, filters, self._norm_axes(), cache_key)
 
     def _norm_axes(self):
@@ -1379,6 +1437,83 @@ class Active:
                 np.ma.MaskedArray(intercept, mask=empty)
             return out
         return trend.slope(parts)
+
+    # -- grouped -----------------------------------------------------------------
+    def _reduce_grouped(self, indexer, compressor, filters, axes):
+        """grouped: one moments record per (output, group).  A unit-step box
+        query whose reduced axes are a leading prefix of the dims takes the
+        dense column kernel over the sorted row list (pyas_group_cols: one
+        finished record per output and group, nothing merged); anything else
+        per-chunk, per-local-group records (pyas_group_axes) merged over
+        host-built segments in chunk order (pyas_moments_combine_segments)."""
+        ds = self.ds
+        gs = self._grouped
+        along, labels, n_g = gs["along"], gs["labels"], gs["n_groups"]
+        self._grouped_path = None
+        final_shape = tuple(1 if i in axes else n for i, n in enumerate(indexer.shape))
+        rshape = tuple(n_g if i == along else n for i, n in enumerate(final_shape))
+        n_rec = int(np.prod(rshape))
+        if n_rec * _lib.MOMENTS_NBYTES > histogram.TABLE_CAP_BYTES:
+            raise ValueError(f"grouped: {int(np.prod(final_shape))} outputs of {n_g} groups need "
+                             f"{n_rec * _lib.MOMENTS_NBYTES} bytes of records, above the cap of "
+                             f"{histogram.TABLE_CAP_BYTES} bytes")
+        if n_rec == 0:
+            return self._format_grouped(np.zeros(rshape, dtype=engine.moments_dtype))
+        q = self._query_plan(indexer, compressor, filters, axes)
+        if q.empty:
+            return self._format_grouped(np.zeros(rshape, dtype=engine.moments_dtype))
+        ctx, st, plan = q.ctx, q.st, q.plan
+        nb = _lib.MOMENTS_NBYTES
+        fin = DeviceBuffer(ctx, n_rec * nb)
+        # the dense path: every dim one unit-step range, reduced axes 0 .. P-1, a kept dim behind them
+        dense = q.dims is not None and len(axes) < ds.ndim and axes == tuple(range(len(axes))) \
+            and bool(np.all(q.table[:, :ds.ndim, 1] == 1))
+        done, keep = False, []
+        if dense:
+            rows = grouped.row_list(q.dims[:len(axes)], ds.chunks, labels, along, n_g)
+            blob = np.concatenate([rows.layer, rows.offset, rows.label, np.zeros(1, dtype=np.int32)])
+            rbuf = DeviceBuffer(ctx, blob.nbytes)
+            ctx.h2d(rbuf.ptr, blob, st)
+            g = _grid_struct(ds.ndim, axes, final_shape, {"n_coords": [len(p) for p in q.dims]}, None, None)
+            done = engine.group_cols(ctx, plan.batch, plan.mask_up.struct, rbuf.ptr, rbuf.ptr + 4 * rows.n_rows,
+                                     rbuf.ptr + 8 * rows.n_rows, rows.n_rows, n_g, g, fin.ptr, st)
+            keep = [rbuf, blob]
+        if not done:
+            projs = itertools.product(*q.dims) if q.dims is not None else (p for _, p in q.chunk_list)
+            cl = grouped.chunk_lists(projs, ds.chunks, labels, along, axes, final_shape, n_g)
+            n = q.n
+            meta = np.concatenate([cl.out_off[:-1], cl.order, cl.seg])
+            lists = np.concatenate([cl.chunk_start, cl.ptr, cl.pos, np.zeros(1, dtype=np.int32)])
+            mbuf = DeviceBuffer(ctx, meta.nbytes)
+            ctx.h2d(mbuf.ptr, meta, st)
+            lbuf = DeviceBuffer(ctx, lists.nbytes)
+            ctx.h2d(lbuf.ptr, lists, st)
+            parts = DeviceBuffer(ctx, max(int(cl.out_off[-1]), 1) * nb)
+            engine.group_axes(ctx, plan.batch, plan.mask_up.struct, lbuf.ptr, lbuf.ptr + 4 * cl.chunk_start.size,
+                              lbuf.ptr + 4 * (cl.chunk_start.size + cl.ptr.size), along, q.axes_mask, mbuf.ptr,
+                              parts.ptr, st)
+            engine.moments_combine_segments(ctx, parts.ptr, mbuf.ptr + 8 * n, mbuf.ptr + 8 * (n + cl.order.size),
+                                            n_rec, fin.ptr, st)
+            keep = [mbuf, lbuf, parts, meta, lists]
+        self._grouped_path = "cols" if done else "walk"
+        final = np.zeros(n_rec, dtype=engine.moments_dtype)
+        ctx.d2h(final, fin.ptr, st)
+        ctx.synchronize(st)
+        del keep
+        # (the dense kernel's records lie group-major over the kept outputs: the reduced dims lead the
+        # kept ones and have extent 1 but for `along`, so that is C order over the result's shape too)
+        return self._format_grouped(final.reshape(rshape))
+
+    def _format_grouped(self, parts):
+        """The result of a grouped query from its records (grouped.finalize),
+        or its components in :meth:`_format_moments`' form."""
+        if self._components:
+            empty = parts["count"] == 0
+            return {"mean": np.ma.MaskedArray(np.ascontiguousarray(parts["mean"]), mask=empty),
+                    "m2": np.ma.MaskedArray(np.ascontiguousarray(parts["m2"]), mask=empty),
+                    "n": np.ma.MaskedArray(np.ascontiguousarray(parts["count"]),
+                                           mask=np.zeros(parts.shape, dtype=bool))}
+        return grouped.finalize(parts, self._grouped["stat"], self._ddof)
 
     # -- histogram ------------------------------------------------------------------
     def _auto_range(self, index, compressor, filters):

@@ -1797,6 +1797,116 @@ int pyas_trend_finalize(pyas_ctx *ctx, const pyas_comoments *in, int64_t n, int3
     return PYAS_OK;
 }
 
+int pyas_group_cols(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask, const pyas_group_rows *rows,
+                    const pyas_grid *g, pyas_moments *out, void *stream) {
+    if (!ctx) return fail(PYAS_EINVAL, "ctx is NULL");
+    if (!g) return fail(PYAS_EINVAL, "grid is NULL");
+    if (batch && (batch->ndim < 1 || batch->ndim > PYAS_MAX_DIMS))
+        return fail(PYAS_ENOTSUP, "chunk rank %d outside 1..%d", batch->ndim, PYAS_MAX_DIMS);
+    pyas::GroupColsArgs x;
+    std::memset(&x, 0, sizeof(x));
+    int es;
+    bool shuf, bsw, masked;
+    int rc = prepare(ctx, batch, mask, x.r, es, shuf, bsw, masked);
+    if (rc) return rc;
+    const int nd = batch->ndim;
+    if (g->ndim != nd) return fail(PYAS_EINVAL, "grid rank %d, chunk rank %d", g->ndim, nd);
+    if (g->axes_mask >> nd) return fail(PYAS_EINVAL, "axes mask 0x%x beyond rank %d", g->axes_mask, nd);
+    if (!rows) return fail(PYAS_EINVAL, "rows is NULL");
+    if (rows->n_rows < 0 || rows->n_groups < 0)
+        return fail(PYAS_EINVAL, "%lld rows, %d groups", (long long)rows->n_rows, rows->n_groups);
+    if (rows->n_rows > 0 && (!rows->layer || !rows->offset || !rows->label))
+        return fail(PYAS_EINVAL, "rows has a NULL table");
+    int64_t n_layers = 1, n_cols = 1, n_out = 1;
+    for (int d = 0; d < nd; ++d) {
+        if (g->n_coords[d] < 1) return fail(PYAS_EINVAL, "n_coords[%d] = %lld", d, (long long)g->n_coords[d]);
+        if ((g->axes_mask >> d) & 1u) {
+            n_layers *= g->n_coords[d];
+        } else {
+            if (g->out_extent[d] < 1) return fail(PYAS_EINVAL, "out_extent[%d] = %lld", d, (long long)g->out_extent[d]);
+            n_cols *= g->n_coords[d];
+            n_out *= g->out_extent[d];
+        }
+    }
+    if (batch->n_chunks != n_layers * n_cols)
+        return fail(PYAS_EINVAL, "%lld chunks for a grid of %lld", (long long)batch->n_chunks,
+                    (long long)(n_layers * n_cols));
+    // the geometries the column walk takes: reduced dims 0 .. P-1, at least one kept dim behind them
+    int P = 0;
+    while (P < nd && ((g->axes_mask >> P) & 1u)) ++P;
+    if (P == 0 || P == nd || g->axes_mask != (1u << P) - 1u)
+        return fail(PYAS_ENOTSUP, "reduced dims 0x%x are not a leading prefix with a kept dim behind it", g->axes_mask);
+    if (x.r.tab.on[0] || x.r.tab.on[1]) return fail(PYAS_ENOTSUP, "vector mask tables");
+    if (rows->n_groups == 0) return PYAS_OK;
+    if (!out) return fail(PYAS_EINVAL, "out is NULL");
+    int64_t items = (batch->chunk_shape[nd - 1] + pyas::kGroupV - 1) / pyas::kGroupV;
+    for (int d = P; d < nd - 1; ++d) items *= batch->chunk_shape[d];
+    const int64_t bpc = (items + pyas::kBlock - 1) / pyas::kBlock;
+    const int64_t grid = n_cols * bpc;
+    if (grid >= (int64_t(1) << 31)) return fail(PYAS_ENOTSUP, "grid of %lld workgroups", (long long)grid);
+    PYAS_HIP(hipSetDevice(ctx->device));
+    x.P = P;
+    x.n_groups = rows->n_groups;
+    x.row_layer = rows->layer;
+    x.row_off = rows->offset;
+    x.row_label = rows->label;
+    x.n_rows = rows->n_rows;
+    int64_t stride = 1;
+    for (int d = nd - 1; d >= 0; --d) {
+        x.n_coords[d] = g->n_coords[d];
+        x.ostride[d] = stride;
+        if (d >= P) stride *= g->out_extent[d];
+    }
+    x.n_layers = n_layers;
+    x.n_cols = n_cols;
+    x.bpc = bpc;
+    x.n_out = n_out;
+    x.out = out;
+    x.bswap = bsw;
+    x.masked = masked;
+    PYAS_HIP(pyas::launch_group_cols(batch->dtype, x, shuf, grid, (hipStream_t)stream));
+    return PYAS_OK;
+}
+
+int pyas_group_axes(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask, const pyas_group_lists *lists,
+                    uint32_t axes_mask, const int64_t *out_offsets, pyas_moments *out, void *stream) {
+    if (!ctx) return fail(PYAS_EINVAL, "ctx is NULL");
+    if (batch && (batch->ndim < 1 || batch->ndim > PYAS_MAX_DIMS))
+        return fail(PYAS_ENOTSUP, "chunk rank %d outside 1..%d", batch->ndim, PYAS_MAX_DIMS);
+    pyas::GroupAxesArgs x;
+    std::memset(&x, 0, sizeof(x));
+    int es;
+    bool shuf, bsw, masked;
+    int rc = prepare(ctx, batch, mask, x.r, es, shuf, bsw, masked);
+    if (rc) return rc;
+    if (axes_mask >> batch->ndim) return fail(PYAS_EINVAL, "axes mask 0x%x beyond rank %d", axes_mask, batch->ndim);
+    if (!lists || !lists->chunk_start || !lists->ptr || !lists->pos)
+        return fail(PYAS_EINVAL, "lists is NULL or has a NULL table");
+    if (lists->dim < 0 || lists->dim >= batch->ndim)
+        return fail(PYAS_EINVAL, "lists dim %d outside rank %d", lists->dim, batch->ndim);
+    if (!((axes_mask >> lists->dim) & 1u))
+        return fail(PYAS_EINVAL, "lists dim %d is not among the reduced dims 0x%x", lists->dim, axes_mask);
+    const int64_t n = batch->n_chunks;
+    if (n == 0) return PYAS_OK;
+    if (!out) return fail(PYAS_EINVAL, "out is NULL");
+    if (!out_offsets) return fail(PYAS_EINVAL, "out_offsets is NULL");
+    PYAS_HIP(hipSetDevice(ctx->device));
+    x.axes = axes_mask;
+    x.out_offsets = out_offsets;
+    x.out = out;
+    x.gstart = lists->chunk_start;
+    x.gptr = lists->ptr;
+    x.gpos = lists->pos;
+    x.gdim = lists->dim;
+    x.shuf = shuf;
+    x.bswap = bsw;
+    axes_geometry(batch->ndim, batch->chunk_shape, axes_mask, x.row, x.bpc);
+    const int64_t grid = n * x.bpc;
+    if (grid >= (int64_t(1) << 31)) return fail(PYAS_ENOTSUP, "grid too large");
+    PYAS_HIP(pyas::launch_group_axes(batch->dtype, x, grid, (hipStream_t)stream));
+    return PYAS_OK;
+}
+
 int pyas_wsum_axes(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask, const pyas_weights *weights,
                    uint32_t axes_mask, const int64_t *out_offsets, pyas_wsum *out, void *stream) {
     if (!ctx) return fail(PYAS_EINVAL, "ctx is NULL");

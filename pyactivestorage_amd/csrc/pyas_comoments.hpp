@@ -8,7 +8,7 @@
 namespace pyas {
 
 struct ComomMerge {
-    // a then b; the means and m2s exactly as MomMerge::merged (pyas_moments.hip)
+    // a then b; the means and m2s exactly as MomMerge::merged (pyas_moments.hpp)
     static __device__ __forceinline__ pyas_comoments merged(const pyas_comoments &a, const pyas_comoments &b) {
         const double na = (double)a.count, nb = (double)b.count;
         const double dx = b.mean_x - a.mean_x, dy = b.mean_y - a.mean_y;

@@ -361,6 +361,40 @@ hipError_t launch_trend_axes(int dtype, const TrendArgs &a, int64_t grid, hipStr
 hipError_t launch_trend_cols(int dtype, const TrendColsArgs &a, bool shuf, int64_t grid, hipStream_t st);
 hipError_t launch_trend_finalize(const pyas_comoments *in, int64_t n, int32_t what, double *value, uint8_t *masked,
                                  hipStream_t st);
+// per-label second moments (pyas_grouped.hip): pyas_moments records, one per (output, group)
+constexpr int kGroupV = 4;            // k_group_cols: consecutive outputs per lane
+constexpr int kGroupRows = PYAS_GROUP_ROWS;   // k_group_cols: rows of the sorted list staged in LDS per pass (16 KiB)
+struct GroupColsArgs {
+    ReduceArgs r;                     // r.out unused; r.sel NULL: whole chunks
+    int32_t P;                        // dims 0 .. P-1 are reduced, P .. ndim-1 kept
+    int32_t n_groups;
+    const int32_t *row_layer;         // pyas_group_rows
+    const int32_t *row_off;
+    const int32_t *row_label;
+    int64_t n_rows;
+    int64_t n_coords[PYAS_MAX_DIMS];  // chunk coordinates per dim (chunk n = C-order position)
+    int64_t ostride[PYAS_MAX_DIMS];   // final-output element strides (kept dims)
+    int64_t n_layers, n_cols;         // chunks along the reduced dims / kept dims
+    int64_t bpc;                      // workgroups per column
+    int64_t n_out;                    // final outputs per group
+    pyas_moments *out;                // out[g * n_out + o]: one finished record per (group, final output)
+    bool bswap, masked;
+};
+struct GroupAxesArgs {
+    ReduceArgs r;                     // r.out unused
+    uint32_t axes;                    // reduced dims (gdim among them)
+    int64_t bpc;                      // workgroups per chunk
+    const int64_t *out_offsets;       // chunk c's records at out[out_offsets[c] + j * n_keep + o]
+    pyas_moments *out;
+    const int32_t *gstart;            // pyas_group_lists
+    const int32_t *gptr;
+    const int32_t *gpos;
+    int32_t gdim;
+    bool shuf, bswap;
+    bool row;                         // innermost dim reduced: a wave per record
+};
+hipError_t launch_group_axes(int dtype, const GroupAxesArgs &a, int64_t grid, hipStream_t st);
+hipError_t launch_group_cols(int dtype, const GroupColsArgs &a, bool shuf, int64_t grid, hipStream_t st);
 // weighted sums (pyas_weighted.hip): count / sum w / sum w x records
 struct WsumArgs {
     ReduceArgs r;                     // r.out unused
