@@ -709,6 +709,28 @@ int pyas_group_axes(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mas
                     const pyas_group_lists *lists, uint32_t axes_mask, const int64_t *out_offsets,
                     pyas_moments *out, void *stream);
 
+/* ---- per-label sums and extremes (Active.grouped "min" / "max" / "sum") -------
+ * pyas_group_cols and pyas_group_axes over pyas_partial records: per (output,
+ * group) the sum (f64 from the first addition for floats, int64 / uint64
+ * wrapping modulo 2^64 for ints), the count, and the NaN-propagating min and
+ * max compared in the variable's type.  The same tables, promises and error
+ * codes; no atomics, every record written once by its owner. */
+
+/* pyas_group_cols for partial records: out[g * n_out + o] is the finished
+ * record of every (group, output); the ALL-ZERO record where group g has no
+ * row (count == 0: min and max are meaningless), so `out` needs no zeroing.
+ * PYAS_ENOTSUP for exactly the geometries pyas_group_cols refuses. */
+int pyas_group_cols_partial(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask,
+                            const pyas_group_rows *rows, const pyas_grid *grid, pyas_partial *out,
+                            void *stream);
+
+/* pyas_group_axes for partial records: one record per (chunk output,
+ * chunk-local group) at out[out_offsets[c] + j * n_keep + o].
+ * pyas_combine_segments with combine_flags = 0 merges them. */
+int pyas_group_axes_partial(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask,
+                            const pyas_group_lists *lists, uint32_t axes_mask,
+                            const int64_t *out_offsets, pyas_partial *out, void *stream);
+
 /* ---- weighted sums (Active.mean / Active.sum with weights=) -----------------
  * Partial record of a weighted mean over a set of elements (32 bytes):
  * count unmasked elements; sw = sum w; swx = sum w x  (f64).  The all-zero

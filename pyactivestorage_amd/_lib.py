@@ -282,6 +282,10 @@ SIGNATURES = {
                         ctypes.POINTER(Grid), _vp, _vp],
     "pyas_group_axes": [_vp, ctypes.POINTER(Batch), ctypes.POINTER(Mask), ctypes.POINTER(GroupLists), _u32, _vp, _vp,
                         _vp],
+    "pyas_group_cols_partial": [_vp, ctypes.POINTER(Batch), ctypes.POINTER(Mask), ctypes.POINTER(GroupRows),
+                                ctypes.POINTER(Grid), _vp, _vp],
+    "pyas_group_axes_partial": [_vp, ctypes.POINTER(Batch), ctypes.POINTER(Mask), ctypes.POINTER(GroupLists), _u32,
+                                _vp, _vp, _vp],
     "pyas_wsum_axes": [_vp, ctypes.POINTER(Batch), ctypes.POINTER(Mask), ctypes.POINTER(Weights), _u32, _vp, _vp,
                        _vp],
     "pyas_wsum_combine_segments": [_vp, _vp, _vp, _vp, _i64, _vp, _vp],

@@ -618,8 +618,8 @@ class Active:
 
     def grouped(self, stat, along, labels, axis=None, ddof=0, n_groups=None):
         """One statistic per label along a reduced dimension, in one pass on
-        the device: ``stat`` (``"mean"``, ``"var"``, ``"std"`` or ``"count"``)
-        of the selected unmasked elements whose global index ``i`` along
+        the device: ``stat`` (``"mean"``, ``"var"``, ``"std"``, ``"count"``,
+        ``"min"``, ``"max"`` or ``"sum"``) of the selected unmasked elements whose global index ``i`` along
         dimension ``along`` has ``labels[i] == g``, for every group ``g`` in
         ``range(G)``: a monthly climatology with ``labels`` the month of each
         time step.  ``along``: an int in ``[-ndim, ndim)`` that must be among
@@ -635,12 +635,24 @@ class Active:
         for ``count`` an int64 ``ndarray``.  An element's value is its float64
         conversion, as for :meth:`var`.  With ``components`` a dict of
         ``mean``, ``m2`` and ``n`` as :meth:`var` returns them, so
-        ``moments.merge`` combines the components of disjoint selections.  A
-        unit-step box query whose reduced axes are a leading prefix of the dims
-        (``along=0, axis=(0,)``) runs the dense column kernel
-        (pyas_group_cols), anything else the per-element walk
-        (pyas_group_axes): see :attr:`grouped_path`.  The settings hold for
-        one query."""
+        ``moments.merge`` combines the components of disjoint selections.
+        ``min`` / ``max`` / ``sum`` (``ddof`` ignored) always return a masked
+        array with a full mask, masked where the group counts no element:
+        ``min`` and ``max`` in the variable's dtype (native byte order),
+        compared in that type (8-byte integers stay exact), NaN where the
+        group counts a NaN as ``np.ma.min`` gives it, the sign of a zero
+        extreme not specified; ``sum`` in ``dtypes.sum_dtype``: int64 / uint64
+        wrapping modulo 2^64 as NumPy's sums, floats added in float64 from
+        the first element and rounded once for a float32 variable.  Their
+        ``components`` are ``sum`` (float64, int64 or uint64), ``min``,
+        ``max`` (the variable's dtype) and ``n``, and
+        ``grouped.merge_partials`` combines the records of disjoint
+        selections.  A unit-step box query whose reduced axes are a leading
+        prefix of the dims (``along=0, axis=(0,)``) runs the dense column
+        kernel (pyas_group_cols, pyas_group_cols_partial for min / max /
+        sum), anything else the per-element walk (pyas_group_axes,
+        pyas_group_axes_partial): see :attr:`grouped_path`.  The settings
+        hold for one query."""
         if stat not in grouped.STATS:
             raise ValueError(f"grouped: stat must be one of {grouped.STATS}. Got {stat!r}")
         ndim = self.ds.ndim
@@ -1449,6 +1461,10 @@ class Active:
         ds = self.ds
         gs = self._grouped
         along, labels, n_g = gs["along"], gs["labels"], gs["n_groups"]
+        # min / max / sum: the same two walks over pyas_partial records (32 bytes as well), merged by
+        # pyas_combine_segments and formatted on the device
+        part = gs["stat"] in grouped.PARTIAL_STATS
+        rdt = engine.partial_dtype(ds.dtype) if part else engine.moments_dtype
         self._grouped_path = None
         final_shape = tuple(1 if i in axes else n for i, n in enumerate(indexer.shape))
         rshape = tuple(n_g if i == along else n for i, n in enumerate(final_shape))
@@ -1458,10 +1474,10 @@ class Active:
                              f"{n_rec * _lib.MOMENTS_NBYTES} bytes of records, above the cap of "
                              f"{histogram.TABLE_CAP_BYTES} bytes")
         if n_rec == 0:
-            return self._format_grouped(np.zeros(rshape, dtype=engine.moments_dtype))
+            return self._format_grouped(np.zeros(rshape, dtype=rdt))
         q = self._query_plan(indexer, compressor, filters, axes)
         if q.empty:
-            return self._format_grouped(np.zeros(rshape, dtype=engine.moments_dtype))
+            return self._format_grouped(np.zeros(rshape, dtype=rdt))
         ctx, st, plan = q.ctx, q.st, q.plan
         nb = _lib.MOMENTS_NBYTES
         fin = DeviceBuffer(ctx, n_rec * nb)
@@ -1476,7 +1492,7 @@ class Active:
             ctx.h2d(rbuf.ptr, blob, st)
             g = _grid_struct(ds.ndim, axes, final_shape, {"n_coords": [len(p) for p in q.dims]}, None, None)
             done = engine.group_cols(ctx, plan.batch, plan.mask_up.struct, rbuf.ptr, rbuf.ptr + 4 * rows.n_rows,
-                                     rbuf.ptr + 8 * rows.n_rows, rows.n_rows, n_g, g, fin.ptr, st)
+                                     rbuf.ptr + 8 * rows.n_rows, rows.n_rows, n_g, g, fin.ptr, st, partial=part)
             keep = [rbuf, blob]
         if not done:
             projs = itertools.product(*q.dims) if q.dims is not None else (p for _, p in q.chunk_list)
@@ -1491,12 +1507,32 @@ class Active:
             parts = DeviceBuffer(ctx, max(int(cl.out_off[-1]), 1) * nb)
             engine.group_axes(ctx, plan.batch, plan.mask_up.struct, lbuf.ptr, lbuf.ptr + 4 * cl.chunk_start.size,
                               lbuf.ptr + 4 * (cl.chunk_start.size + cl.ptr.size), along, q.axes_mask, mbuf.ptr,
-                              parts.ptr, st)
-            engine.moments_combine_segments(ctx, parts.ptr, mbuf.ptr + 8 * n, mbuf.ptr + 8 * (n + cl.order.size),
-                                            n_rec, fin.ptr, st)
+                              parts.ptr, st, partial=part)
+            if part:   # (no rounding to the variable dtype between chunks: the f64 sum is rounded once, at the end)
+                engine.combine_segments(ctx, ds.dtype, parts.ptr, mbuf.ptr + 8 * n,
+                                        mbuf.ptr + 8 * (n + cl.order.size), n_rec, fin.ptr, False, st)
+            else:
+                engine.moments_combine_segments(ctx, parts.ptr, mbuf.ptr + 8 * n,
+                                                mbuf.ptr + 8 * (n + cl.order.size), n_rec, fin.ptr, st)
             keep = [mbuf, lbuf, parts, meta, lists]
         self._grouped_path = "cols" if done else "walk"
-        final = np.zeros(n_rec, dtype=engine.moments_dtype)
+        if part and not self._components:
+            # the value and its mask on the device: 2 to 9 bytes per record come back instead of 32
+            stat = gs["stat"]
+            vdt = engine.format_dtype(ds.dtype, stat)
+            vbuf = DeviceBuffer(ctx, n_rec * (vdt.itemsize + 1))
+            engine.format_partials(ctx, ds.dtype, fin.ptr, n_rec, stat, vbuf.ptr, vbuf.ptr + n_rec * vdt.itemsize,
+                                   None, st)
+            val = np.empty(n_rec, dtype=vdt)
+            msk = np.empty(n_rec, dtype=np.uint8)
+            ctx.d2h(val, vbuf.ptr, st)
+            ctx.d2h(msk, vbuf.ptr + n_rec * vdt.itemsize, st)
+            ctx.synchronize(st)
+            del keep
+            msk = msk.astype(bool)
+            val[msk] = 0   # (a group that counts nothing holds no value: 0 under the mask, as an empty query gives)
+            return np.ma.MaskedArray(val.reshape(rshape), mask=msk.reshape(rshape))
+        final = np.zeros(n_rec, dtype=rdt)
         ctx.d2h(final, fin.ptr, st)
         ctx.synchronize(st)
         del keep
@@ -1506,7 +1542,18 @@ class Active:
 
     def _format_grouped(self, parts):
         """The result of a grouped query from its records (grouped.finalize),
-        or its components in :meth:`_format_moments`' form."""
+        or its components in :meth:`_format_moments`' form (min / max / sum:
+        the whole partial records' ``sum``, ``min``, ``max`` and ``n``)."""
+        stat = self._grouped["stat"]
+        if stat in grouped.PARTIAL_STATS:
+            if not self._components:
+                return grouped.finalize(parts, stat, self._ddof, dtype=self.ds.dtype)
+            empty = parts["count"] == 0
+            out = {"sum": grouped.finalize(parts, "sum")}   # (the record's own 8-byte sum)
+            for name in ("min", "max"):
+                out[name] = grouped.finalize(parts, name, dtype=self.ds.dtype)
+            out["n"] = np.ma.MaskedArray(np.ascontiguousarray(parts["count"]), mask=np.zeros(parts.shape, dtype=bool))
+            return out
         if self._components:
             empty = parts["count"] == 0
             return {"mean": np.ma.MaskedArray(np.ascontiguousarray(parts["mean"]), mask=empty),

@@ -1797,8 +1797,11 @@ int pyas_trend_finalize(pyas_ctx *ctx, const pyas_comoments *in, int64_t n, int3
     return PYAS_OK;
 }
 
-int pyas_group_cols(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask, const pyas_group_rows *rows,
-                    const pyas_grid *g, pyas_moments *out, void *stream) {
+// pyas_group_cols / pyas_group_cols_partial: the checks and the geometry, then
+// `launch` (launch_group_cols or launch_group_cols_partial) over `out`
+typedef hipError_t (*group_cols_launch)(int, const pyas::GroupColsArgs &, bool, int64_t, hipStream_t);
+static int group_cols_run(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask, const pyas_group_rows *rows,
+                          const pyas_grid *g, void *out, void *stream, group_cols_launch launch) {
     if (!ctx) return fail(PYAS_EINVAL, "ctx is NULL");
     if (!g) return fail(PYAS_EINVAL, "grid is NULL");
     if (batch && (batch->ndim < 1 || batch->ndim > PYAS_MAX_DIMS))
@@ -1864,12 +1867,25 @@ int pyas_group_cols(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mas
     x.out = out;
     x.bswap = bsw;
     x.masked = masked;
-    PYAS_HIP(pyas::launch_group_cols(batch->dtype, x, shuf, grid, (hipStream_t)stream));
+    PYAS_HIP(launch(batch->dtype, x, shuf, grid, (hipStream_t)stream));
     return PYAS_OK;
 }
 
-int pyas_group_axes(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask, const pyas_group_lists *lists,
-                    uint32_t axes_mask, const int64_t *out_offsets, pyas_moments *out, void *stream) {
+int pyas_group_cols(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask, const pyas_group_rows *rows,
+                    const pyas_grid *g, pyas_moments *out, void *stream) {
+    return group_cols_run(ctx, batch, mask, rows, g, out, stream, pyas::launch_group_cols);
+}
+
+int pyas_group_cols_partial(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask,
+                            const pyas_group_rows *rows, const pyas_grid *g, pyas_partial *out, void *stream) {
+    return group_cols_run(ctx, batch, mask, rows, g, out, stream, pyas::launch_group_cols_partial);
+}
+
+// pyas_group_axes / pyas_group_axes_partial, as group_cols_run
+typedef hipError_t (*group_axes_launch)(int, const pyas::GroupAxesArgs &, int64_t, hipStream_t);
+static int group_axes_run(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask, const pyas_group_lists *lists,
+                          uint32_t axes_mask, const int64_t *out_offsets, void *out, void *stream,
+                          group_axes_launch launch) {
     if (!ctx) return fail(PYAS_EINVAL, "ctx is NULL");
     if (batch && (batch->ndim < 1 || batch->ndim > PYAS_MAX_DIMS))
         return fail(PYAS_ENOTSUP, "chunk rank %d outside 1..%d", batch->ndim, PYAS_MAX_DIMS);
@@ -1903,8 +1919,20 @@ int pyas_group_axes(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mas
     axes_geometry(batch->ndim, batch->chunk_shape, axes_mask, x.row, x.bpc);
     const int64_t grid = n * x.bpc;
     if (grid >= (int64_t(1) << 31)) return fail(PYAS_ENOTSUP, "grid too large");
-    PYAS_HIP(pyas::launch_group_axes(batch->dtype, x, grid, (hipStream_t)stream));
+    PYAS_HIP(launch(batch->dtype, x, grid, (hipStream_t)stream));
     return PYAS_OK;
+}
+
+int pyas_group_axes(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask, const pyas_group_lists *lists,
+                    uint32_t axes_mask, const int64_t *out_offsets, pyas_moments *out, void *stream) {
+    return group_axes_run(ctx, batch, mask, lists, axes_mask, out_offsets, out, stream, pyas::launch_group_axes);
+}
+
+int pyas_group_axes_partial(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask,
+                            const pyas_group_lists *lists, uint32_t axes_mask, const int64_t *out_offsets,
+                            pyas_partial *out, void *stream) {
+    return group_axes_run(ctx, batch, mask, lists, axes_mask, out_offsets, out, stream,
+                          pyas::launch_group_axes_partial);
 }
 
 int pyas_wsum_axes(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask, const pyas_weights *weights,

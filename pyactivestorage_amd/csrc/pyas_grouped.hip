@@ -1,5 +1,11 @@
-// pyas_grouped.hip — per-label second moments behind Active.grouped
-// (pyas_group_cols and pyas_group_axes of include/pyas.h).
+// pyas_grouped.hip — per-label statistics behind Active.grouped
+// (pyas_group_cols / pyas_group_axes and their _partial forms, include/pyas.h).
+//
+// Two records over the same two walks, the accumulator a template argument:
+// MomAcc -> pyas_moments (mean / var / std / count) and PartAcc<T> ->
+// pyas_partial (sum / count / min / max).  The walks below are written once;
+// k_group_cols and k_group_axes are the MomAcc instances under their old
+// names, k_group_cols_partial and k_group_axes_partial the PartAcc ones.
 //
 // The pyas_moments record of pyas_moments.hip (count / mean / m2, MomAcc per
 // lane, MomMerge above a lane), one record per (output, label): an element at
@@ -46,6 +52,14 @@
 //                (innermost dim reduced).  pyas_moments_combine_segments
 //                merges the records.  Correct, no speed target.  Templated on
 //                the dtype only (10 kernels).
+// PartAcc<T>   : AccT<T, uint32_t> of pyas_device.hpp per lane: the sum in
+//                TT<T>::Acc (f64 from the first addition for floats, int64 /
+//                uint64 wrapping for ints), min and max compared in T with
+//                pmin / pmax (NaN-propagating), one element per call: a
+//                column lane sees one element per row, so there is no f32
+//                group of four and no hunt for a shift.  One kernel per dtype
+//                carries all four fields (18 + 10 kernels); sum, min and max
+//                are picked by pyas_format_partials afterwards.
 #include <hip/hip_runtime.h>
 
 #include "pyas_moments.hpp"     // MomMerge, MomAcc
@@ -55,15 +69,94 @@
 namespace pyas {
 
 // ---------------------------------------------------------------------------
+// the two accumulators behind one interface
+// ---------------------------------------------------------------------------
+// sum / count / min / max of one (output, group) in a lane
+template <typename T>
+struct PartAcc {
+    Acc<T> a;
+    __device__ __forceinline__ void init() { a.init(); }
+    __device__ __forceinline__ void add(T x, bool ok) { a.add_flag(x, !ok); }
+    // (count == 0 leaves sum 0 and the neutral extremes, which merge as nothing)
+    __device__ __forceinline__ pyas_partial finish() const {
+        pyas_partial p;
+        TT<T>::put_acc(p.sum, a.sum);
+        p.count = (int64_t)a.count;
+        TT<T>::put(p.min, a.mn);
+        TT<T>::put(p.max, a.mx);
+        return p;
+    }
+};
+
+template <typename T>
+struct PartMerge {
+    // a then b (a float sum's last bit depends on the order, so every caller fixes it)
+    static __device__ __forceinline__ pyas_partial merged(const pyas_partial &a, const pyas_partial &b) {
+        pyas_partial r;
+        if constexpr (TT<T>::kind == 0) r.sum.f = a.sum.f + b.sum.f;
+        else r.sum.u = a.sum.u + b.sum.u;   // two's complement: the signed sum wraps the same way
+        r.count = a.count + b.count;
+        TT<T>::put(r.min, pmin(TT<T>::from(a.min), TT<T>::from(b.min)));
+        TT<T>::put(r.max, pmax(TT<T>::from(a.max), TT<T>::from(b.max)));
+        if (b.count == 0) r = a;         // an empty side is skipped: its extremes mean nothing
+        else if (a.count == 0) r = b;
+        return r;
+    }
+    static __device__ __forceinline__ pyas_partial shfl_xor(const pyas_partial &p, int m) {
+        pyas_partial q;
+        q.sum.u = pyas::shfl_xor(p.sum.u, m);
+        q.count = pyas::shfl_xor(p.count, m);
+        q.min.u = pyas::shfl_xor(p.min.u, m);
+        q.max.u = pyas::shfl_xor(p.max.u, m);
+        return q;
+    }
+};
+
+// What a walk needs to know of its accumulator: the record, its merge, its
+// zero, and whether the lane hunts for a shift (MomAcc's K) at a run's start.
+template <typename A> struct GrRec;
+template <> struct GrRec<MomAcc> {
+    using R = pyas_moments;
+    using Merge = MomMerge;
+    static constexpr bool kHunt = true;
+    static __device__ __forceinline__ pyas_moments zero() {
+        pyas_moments z;
+        z.count = 0;
+        z.mean = 0.0;
+        z.m2 = 0.0;
+        z.reserved = 0;
+        return z;
+    }
+};
+template <typename T> struct GrRec<PartAcc<T>> {
+    using R = pyas_partial;
+    using Merge = PartMerge<T>;
+    static constexpr bool kHunt = false;
+    static __device__ __forceinline__ pyas_partial zero() {
+        pyas_partial z;
+        z.sum.u = 0;
+        z.count = 0;
+        z.min.u = 0;
+        z.max.u = 0;
+        return z;
+    }
+};
+
+template <typename T>
+__device__ __forceinline__ void gr_add(MomAcc &acc, T x, bool ok) { acc.add_one((double)x, ok); }
+template <typename T>
+__device__ __forceinline__ void gr_add(PartAcc<T> &acc, T x, bool ok) { acc.add(x, ok); }
+
+// ---------------------------------------------------------------------------
 // k_group_axes: the per-element walk
 // ---------------------------------------------------------------------------
 // Positions q0, q0 + stride, ... < n_pos over the dims in `red`, the dim gdim
 // counting the glen entries of gp (positions among the selected indices along
 // gdim) instead of the dim's whole selection; bo: the kept dims' part.
-template <typename T>
+template <typename T, typename A>
 __device__ __forceinline__ void gr_walk(const ReduceArgs &r, const uint8_t *base, const Sel &s, uint32_t red, int gdim,
                                         const int32_t *gp, uint32_t glen, const Decomp &bo, int64_t q0, int64_t n_pos,
-                                        int64_t stride, bool shuf, bool bsw, const MaskT<T> &mk, MomAcc &acc) {
+                                        int64_t stride, bool shuf, bool bsw, const MaskT<T> &mk, A &acc) {
     for (int64_t q = q0; q < n_pos; q += stride) {
         Decomp od = bo;
         uint32_t e = (uint32_t)q;   // < the chunk's elements < 2^31
@@ -81,12 +174,13 @@ __device__ __forceinline__ void gr_walk(const ReduceArgs &r, const uint8_t *base
             }
         }
         const T x = load_elem_rt<T>(base, r.chunk_elems, od.mem, shuf, bsw);
-        acc.add_one((double)x, !all_masked(mk, r.tab, od, x));
+        gr_add(acc, x, !all_masked(mk, r.tab, od, x));
     }
 }
 
-template <typename T>
-__global__ __launch_bounds__(kBlock) void k_group_axes(GroupAxesArgs a) {
+template <typename T, typename A>
+__device__ __forceinline__ void group_axes_body(const GroupAxesArgs &a) {
+    using R = typename GrRec<A>::R;
     const ReduceArgs &r = a.r;
     const int64_t c = (int64_t)blockIdx.x / a.bpc, b = (int64_t)blockIdx.x % a.bpc;
     const uint8_t *base = r.data + r.offsets[c];
@@ -104,17 +198,17 @@ __global__ __launch_bounds__(kBlock) void k_group_axes(GroupAxesArgs a) {
     const int64_t n_rest = cnt_g > 0 ? n_red / cnt_g : 0;   // the other reduced dims' positions
     const int32_t g0 = a.gstart[c];
     const int64_t n_rec = n_keep * (a.gstart[c + 1] - g0);
-    pyas_moments *out = a.out + a.out_offsets[c];
+    R *out = static_cast<R *>(a.out) + a.out_offsets[c];
     if (!a.row) {   // a lane per record, adjacent lanes at adjacent outputs
         for (int64_t rec = b * kBlock + threadIdx.x; rec < n_rec; rec += a.bpc * kBlock) {
             const int64_t j = rec / n_keep, o = rec - j * n_keep;
             const int32_t p0 = a.gptr[g0 + j], len = a.gptr[g0 + j + 1] - p0;
-            MomAcc acc;
+            A acc;
             acc.init();
             if (n_rest * len > 0) {
                 Decomp bo{0, {0, 0}};
                 decompose(s, r.pool, r.cstride, r.tab, r.ndim, keep, o, bo);
-                gr_walk<T>(r, base, s, red, a.gdim, a.gpos + p0, (uint32_t)len, bo, 0, n_rest * len, 1, a.shuf, a.bswap,
+                gr_walk<T, A>(r, base, s, red, a.gdim, a.gpos + p0, (uint32_t)len, bo, 0, n_rest * len, 1, a.shuf, a.bswap,
                            mk, acc);
             }
             out[rec] = acc.finish();
@@ -125,19 +219,29 @@ __global__ __launch_bounds__(kBlock) void k_group_axes(GroupAxesArgs a) {
         for (int64_t rec = b * kWaves + threadIdx.x / kWave; rec < n_rec; rec += a.bpc * kWaves) {
             const int64_t j = rec / n_keep, o = rec - j * n_keep;
             const int32_t p0 = a.gptr[g0 + j], len = a.gptr[g0 + j + 1] - p0;
-            MomAcc acc;
+            A acc;
             acc.init();
             if (lane < n_rest * len) {
                 Decomp bo{0, {0, 0}};
                 decompose(s, r.pool, r.cstride, r.tab, r.ndim, keep, o, bo);
-                gr_walk<T>(r, base, s, red, a.gdim, a.gpos + p0, (uint32_t)len, bo, lane, n_rest * len, kWave, a.shuf,
+                gr_walk<T, A>(r, base, s, red, a.gdim, a.gpos + p0, (uint32_t)len, bo, lane, n_rest * len, kWave, a.shuf,
                            a.bswap, mk, acc);
             }
-            pyas_moments p = acc.finish();
-            rec_wave_merge<pyas_moments, MomMerge>(p);
+            R p = acc.finish();
+            rec_wave_merge<R, typename GrRec<A>::Merge>(p);
             if (lane == 0) out[rec] = p;
         }
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_group_axes(GroupAxesArgs a) {
+    group_axes_body<T, MomAcc>(a);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_group_axes_partial(GroupAxesArgs a) {
+    group_axes_body<T, PartAcc<T>>(a);
 }
 
 // ---------------------------------------------------------------------------
@@ -181,27 +285,26 @@ __device__ __forceinline__ void gr_fetch(const uint8_t *data, int64_t n, int64_t
 }
 
 // The lane's state along the sorted row list.
+template <typename A>
 struct GrLane {
-    MomAcc acc[kGroupV];
+    A acc[kGroupV];
     int32_t cur;    // the label of the run being accumulated, -1 before the first
-    bool hunt;      // some output of the wave still looks for its shift
+    bool hunt;      // some output of the wave still looks for its shift (MomAcc only)
 };
 
 // The run of label ln.cur is over and the next row's label is `next` (the
 // group count behind the last run): the finished records of ln.cur, the zero
 // records of the labels in between, and fresh accumulators.
-__device__ __forceinline__ void gr_advance(GrLane &ln, const bool *in, pyas_moments *out, int64_t n_out, int32_t next) {
+template <typename A>
+__device__ __forceinline__ void gr_advance(GrLane<A> &ln, const bool *in, typename GrRec<A>::R *out, int64_t n_out,
+                                           int32_t next) {
     constexpr int V = kGroupV;
     if (ln.cur >= 0) {
 #pragma unroll
         for (int k = 0; k < V; ++k)
             if (in[k]) out[(int64_t)ln.cur * n_out + k] = ln.acc[k].finish();
     }
-    pyas_moments zero;
-    zero.count = 0;
-    zero.mean = 0.0;
-    zero.m2 = 0.0;
-    zero.reserved = 0;
+    const typename GrRec<A>::R zero = GrRec<A>::zero();
     for (int32_t g = ln.cur + 1; g < next; ++g) {
 #pragma unroll
         for (int k = 0; k < V; ++k)
@@ -217,10 +320,10 @@ __device__ __forceinline__ void gr_advance(GrLane &ln, const bool *in, pyas_mome
 // selected, vec_lane: all of them and the chunks' rows are a multiple of 4
 // elements.  Register double buffer: the next U rows' loads are in flight
 // while these U rows are accumulated (8-byte types keep one buffer).
-template <typename T, bool SHUF, bool BSW, int M>
+template <typename T, bool SHUF, bool BSW, int M, typename A>
 __device__ __forceinline__ void gr_rows(const uint8_t *data, int64_t n, int64_t kmem, bool vec_lane, const bool *in,
                                         const int64_t *cb, const int32_t *roff, const int32_t *lab, int nq,
-                                        const MaskT<T> &mk, pyas_moments *out, int64_t n_out, GrLane &ln) {
+                                        const MaskT<T> &mk, typename GrRec<A>::R *out, int64_t n_out, GrLane<A> &ln) {
     constexpr int U = GrRows<T>::U, V = kGroupV;
     constexpr bool DB = sizeof(T) < 8;
     GrRows<T> cur, nxt;
@@ -236,8 +339,14 @@ __device__ __forceinline__ void gr_rows(const uint8_t *data, int64_t n, int64_t 
             if (q + u < nq) {   // (uniform)
                 const int32_t g = lab[q + u];
                 if (g != ln.cur) gr_advance(ln, in, out, n_out, g);   // (uniform over the workgroup)
+                if constexpr (!GrRec<A>::kHunt) {   // no shift: every element goes the same way
+#pragma unroll
+                    for (int k = 0; k < V; ++k) {
+                        const T v = cur.v[u][k];
+                        gr_add(ln.acc[k], v, in[k] && (M == 0 || !mk.template masked_m<M ? M : kMaskAll>(v)));
+                    }
                 // once every output of the wave has its shift it is no longer looked for
-                if (__builtin_expect(ln.hunt, 0)) {
+                } else if (__builtin_expect(ln.hunt, 0)) {
                     bool first = false;
 #pragma unroll
                     for (int k = 0; k < V; ++k) {
@@ -259,112 +368,28 @@ __device__ __forceinline__ void gr_rows(const uint8_t *data, int64_t n, int64_t 
     }
 }
 
-template <typename T, bool SHUF, bool BSW>
+template <typename T, bool SHUF, bool BSW, typename A>
 __device__ __forceinline__ void gr_rows_m(int mode, const uint8_t *data, int64_t n, int64_t kmem, bool vec_lane,
                                           const bool *in, const int64_t *cb, const int32_t *roff, const int32_t *lab,
-                                          int nq, const MaskT<T> &mk, pyas_moments *out, int64_t n_out, GrLane &ln) {
+                                          int nq, const MaskT<T> &mk, typename GrRec<A>::R *out, int64_t n_out,
+                                          GrLane<A> &ln) {
     if (mode == 0) gr_rows<T, SHUF, BSW, 0>(data, n, kmem, vec_lane, in, cb, roff, lab, nq, mk, out, n_out, ln);
     else if (mode == kMaskRange)
         gr_rows<T, SHUF, BSW, kMaskRange>(data, n, kmem, vec_lane, in, cb, roff, lab, nq, mk, out, n_out, ln);
     else gr_rows<T, SHUF, BSW, kMaskAll>(data, n, kmem, vec_lane, in, cb, roff, lab, nq, mk, out, n_out, ln);
 }
 
+// (the body is included, not called: see pyas_group_cols_body.inc)
 template <typename T, bool SHUF>
 __global__ __launch_bounds__(kBlock) void k_group_cols(GroupColsArgs a) {
-    constexpr int V = kGroupV;
-    const ReduceArgs &r = a.r;
-    const int nd = r.ndim, P = a.P, L = nd - 1;
-    const int64_t col = (int64_t)blockIdx.x / a.bpc, sb = (int64_t)blockIdx.x % a.bpc;
-    // The kept dims' selection is the same in every layer of the column: read
-    // it from layer 0 (chunk `col`).
-    Sel s0;
-    load_sel(s0, r.sel, col, nd, r.shape);
-    int64_t KO = 1;
-#pragma unroll
-    for (int d = 0; d < PYAS_MAX_DIMS; ++d)
-        if (d >= P && d < L) KO *= s0.cnt[d];
-    int32_t st = 0, cn = 0;   // the innermost dim's selection
-#pragma unroll
-    for (int d = 0; d < PYAS_MAX_DIMS; ++d)
-        if (d == L) {
-            st = s0.start[d];
-            cn = s0.cnt[d];
-        }
-    const int32_t g0 = st / V;
-    const int32_t G = cn > 0 ? (st + cn - 1) / V - g0 + 1 : 0;   // groups of 4 chunk elements the row's selection touches
-    const int64_t n_items = KO * G;
-    if (sb * kBlock >= n_items) return;   // (uniform) nothing for this workgroup
-    const int64_t item = sb * kBlock + threadIdx.x;
-    const bool live = item < n_items;
-    int64_t ko = live ? item / G : 0;
-    const int32_t g = live ? (int32_t)(item - ko * G) : 0;
-    const int32_t i0 = (g0 + g) * V;   // the innermost chunk index of the lane's first output
-    bool in[V], full = true;
-#pragma unroll
-    for (int k = 0; k < V; ++k) {
-        in[k] = live && i0 + k >= st && i0 + k < st + cn;
-        full = full && in[k];
-    }
-    // the kept dims' part: chunk memory and the final output index of output 0
-    // (as k_trend_cols)
-    int64_t kmem = i0, fidx = 0;
-    {
-        int64_t rest = col, cs = 1;
-#pragma unroll
-        for (int d = PYAS_MAX_DIMS - 1; d >= 0; --d) {
-            if (d < nd && d >= P) {
-                const int64_t nc = a.n_coords[d];
-                const int64_t ad = rest % nc;
-                rest /= nc;
-                const int64_t first = col - ad * cs;
-                const int64_t st0 = r.sel ? r.sel[(first * PYAS_MAX_DIMS + d) * 3] : 0;
-                const int64_t ostart = ad == 0 ? 0 : (r.shape[d] - st0) + (ad - 1) * r.shape[d];
-                cs *= nc;
-                if (d == L) {
-                    fidx += (ostart + (i0 - st)) * a.ostride[d];
-                } else {
-                    const int64_t cd = s0.cnt[d];
-                    const int64_t qq = ko / cd, k = ko - qq * cd;
-                    ko = qq;
-                    kmem += (s0.start[d] + k) * r.cstride[d];
-                    fidx += (ostart + k) * a.ostride[d];
-                }
-            }
-        }
-    }
-    MaskT<T> mk;
-    // (left as a call, init would take the address of the kernel arguments and keep a copy of them in scratch)
-    [[clang::always_inline]] mk.init(r.mask);
-    const int mode = mask_mode(a.masked, r.mask.flags);
-    const bool vec_lane = full && (r.shape[L] % V) == 0;
-    __shared__ int64_t s_cb[kGroupRows];
-    __shared__ int32_t s_roff[kGroupRows];
-    __shared__ int32_t s_lab[kGroupRows];
-    GrLane ln;
-#pragma unroll
-    for (int k = 0; k < V; ++k) ln.acc[k].init();
-    ln.cur = -1;
-    ln.hunt = true;
-    pyas_moments *out = a.out + fidx;   // the lane's 4 outputs are adjacent: the innermost dim's output stride is 1
-    for (int64_t t0 = 0; t0 < a.n_rows; t0 += kGroupRows) {
-        const int nq = (int)(a.n_rows - t0 < kGroupRows ? a.n_rows - t0 : kGroupRows);
-        __syncthreads();   // the previous pass has been read
-        for (int q = threadIdx.x; q < nq; q += kBlock) {
-            s_cb[q] = r.offsets[(int64_t)a.row_layer[t0 + q] * a.n_cols + col];
-            s_roff[q] = a.row_off[t0 + q];
-            s_lab[q] = a.row_label[t0 + q];
-        }
-        __syncthreads();
-        if (live) {
-            if (a.bswap)
-                gr_rows_m<T, SHUF, true>(mode, r.data, r.chunk_elems, kmem, vec_lane, in, s_cb, s_roff, s_lab, nq, mk, out,
-                                         a.n_out, ln);
-            else
-                gr_rows_m<T, SHUF, false>(mode, r.data, r.chunk_elems, kmem, vec_lane, in, s_cb, s_roff, s_lab, nq, mk, out,
-                                          a.n_out, ln);
-        }
-    }
-    if (live) gr_advance(ln, in, out, a.n_out, a.n_groups);   // the last run and the labels behind it
+    using A = MomAcc;
+#include "pyas_group_cols_body.inc"
+}
+
+template <typename T, bool SHUF>
+__global__ __launch_bounds__(kBlock) void k_group_cols_partial(GroupColsArgs a) {
+    using A = PartAcc<T>;
+#include "pyas_group_cols_body.inc"
 }
 
 // ---------------------------------------------------------------------------
@@ -382,6 +407,20 @@ hipError_t launch_group_axes(int dtype, const GroupAxesArgs &a, int64_t grid, hi
 
 hipError_t launch_group_cols(int dtype, const GroupColsArgs &a, bool shuf, int64_t grid, hipStream_t st) {
     PYAS_DISPATCH_DTYPE(launch_shuf, PYAS_SHUF_KERNEL(k_group_cols), a, shuf, grid, 0, st)
+}
+
+template <typename T>
+hipError_t launch_gr_axes_partial_t(const GroupAxesArgs &a, int64_t grid, hipStream_t st) {
+    hipLaunchKernelGGL((k_group_axes_partial<T>), dim3((unsigned)grid), dim3(kBlock), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_group_axes_partial(int dtype, const GroupAxesArgs &a, int64_t grid, hipStream_t st) {
+    PYAS_DISPATCH_DTYPE(launch_gr_axes_partial_t, a, grid, st)
+}
+
+hipError_t launch_group_cols_partial(int dtype, const GroupColsArgs &a, bool shuf, int64_t grid, hipStream_t st) {
+    PYAS_DISPATCH_DTYPE(launch_shuf, PYAS_SHUF_KERNEL(k_group_cols_partial), a, shuf, grid, 0, st)
 }
 
 }  // namespace pyas

@@ -377,7 +377,8 @@ struct GroupColsArgs {
     int64_t n_layers, n_cols;         // chunks along the reduced dims / kept dims
     int64_t bpc;                      // workgroups per column
     int64_t n_out;                    // final outputs per group
-    pyas_moments *out;                // out[g * n_out + o]: one finished record per (group, final output)
+    void *out;                        // out[g * n_out + o]: one finished record per (group, final output);
+                                      // pyas_moments (k_group_cols) or pyas_partial (k_group_cols_partial)
     bool bswap, masked;
 };
 struct GroupAxesArgs {
@@ -385,7 +386,7 @@ struct GroupAxesArgs {
     uint32_t axes;                    // reduced dims (gdim among them)
     int64_t bpc;                      // workgroups per chunk
     const int64_t *out_offsets;       // chunk c's records at out[out_offsets[c] + j * n_keep + o]
-    pyas_moments *out;
+    void *out;                        // pyas_moments (k_group_axes) or pyas_partial (k_group_axes_partial)
     const int32_t *gstart;            // pyas_group_lists
     const int32_t *gptr;
     const int32_t *gpos;
@@ -395,6 +396,9 @@ struct GroupAxesArgs {
 };
 hipError_t launch_group_axes(int dtype, const GroupAxesArgs &a, int64_t grid, hipStream_t st);
 hipError_t launch_group_cols(int dtype, const GroupColsArgs &a, bool shuf, int64_t grid, hipStream_t st);
+// per-label sum / count / min / max (pyas_grouped.hip): the same walks over pyas_partial records
+hipError_t launch_group_axes_partial(int dtype, const GroupAxesArgs &a, int64_t grid, hipStream_t st);
+hipError_t launch_group_cols_partial(int dtype, const GroupColsArgs &a, bool shuf, int64_t grid, hipStream_t st);
 // weighted sums (pyas_weighted.hip): count / sum w / sum w x records
 struct WsumArgs {
     ReduceArgs r;                     // r.out unused

@@ -294,28 +294,33 @@ def trend_finalize(ctx: Context, in_ptr, n: int, what: int, value_ptr, mask_ptr,
 
 
 def group_cols(ctx: Context, batch: _lib.Batch, mask: _lib.Mask, layer_ptr, offset_ptr, label_ptr, n_rows: int,
-               n_groups: int, grid: _lib.Grid, out_ptr, stream) -> bool:
+               n_groups: int, grid: _lib.Grid, out_ptr, stream, partial: bool = False) -> bool:
     """pyas_group_cols: one finished moments record per (group, final output)
     of a unit-step box query, in one launch, over the sorted row list
     (``grouped.row_list``).  False (nothing launched) when the geometry is not
-    the dense path's (PYAS_ENOTSUP): the caller runs :func:`group_axes`."""
+    the dense path's (PYAS_ENOTSUP): the caller runs :func:`group_axes`.
+    ``partial``: pyas_group_cols_partial, the same over ``partial_dtype``
+    records."""
+    name = "pyas_group_cols_partial" if partial else "pyas_group_cols"
     rows = _lib.GroupRows(layer_ptr, offset_ptr, label_ptr, int(n_rows), int(n_groups))
-    rc = ctx.lib.pyas_group_cols(ctx.handle, ctypes.byref(batch), ctypes.byref(mask), ctypes.byref(rows),
-                                 ctypes.byref(grid), out_ptr, stream)
+    rc = getattr(ctx.lib, name)(ctx.handle, ctypes.byref(batch), ctypes.byref(mask), ctypes.byref(rows),
+                                ctypes.byref(grid), out_ptr, stream)
     if rc == _lib.ENOTSUP:
         return False
-    _lib.check(rc, "pyas_group_cols")
+    _lib.check(rc, name)
     return True
 
 
 def group_axes(ctx: Context, batch: _lib.Batch, mask: _lib.Mask, start_ptr, ptr_ptr, pos_ptr, dim: int,
-               axes_mask: int, out_offsets_ptr, out_ptr, stream) -> None:
+               axes_mask: int, out_offsets_ptr, out_ptr, stream, partial: bool = False) -> None:
     """pyas_group_axes: moments records per (chunk output, chunk-local group);
     ``start_ptr`` / ``ptr_ptr`` / ``pos_ptr`` / ``dim``: pyas_group_lists
-    (``grouped.chunk_lists``)."""
+    (``grouped.chunk_lists``).  ``partial``: pyas_group_axes_partial, the same
+    over ``partial_dtype`` records."""
+    name = "pyas_group_axes_partial" if partial else "pyas_group_axes"
     lists = _lib.GroupLists(start_ptr, ptr_ptr, pos_ptr, int(dim))
-    _lib.check(ctx.lib.pyas_group_axes(ctx.handle, ctypes.byref(batch), ctypes.byref(mask), ctypes.byref(lists),
-                                       int(axes_mask), out_offsets_ptr, out_ptr, stream), "pyas_group_axes")
+    _lib.check(getattr(ctx.lib, name)(ctx.handle, ctypes.byref(batch), ctypes.byref(mask), ctypes.byref(lists),
+                                      int(axes_mask), out_offsets_ptr, out_ptr, stream), name)
 
 
 def hist_axes(ctx: Context, batch: _lib.Batch, mask: _lib.Mask, edges_ptr, n_bins: int, uniform, axes_mask: int,

@@ -15,11 +15,51 @@ from types import SimpleNamespace
 import numpy as np
 
 from . import moments
+from .dtypes import native, sum_dtype
 from .engine import moments_dtype
 
-STATS = ("mean", "var", "std", "count")
+STATS = ("mean", "var", "std", "count", "min", "max", "sum")
+# the stats whose record is ``engine.partial_dtype`` (``pyas_partial``): per
+# (output, group) the sum, the count and the NaN-propagating min and max
+PARTIAL_STATS = ("min", "max", "sum")
 
 merge = moments.merge
+
+
+def _pmin(a, b):
+    """NaN-propagating minimum, elementwise, in the arrays' own type."""
+    if a.dtype.kind == "f":
+        return np.where(np.isnan(a), a, np.where(np.isnan(b), b, np.where(b < a, b, a)))
+    return np.where(b < a, b, a)
+
+
+def _pmax(a, b):
+    if a.dtype.kind == "f":
+        return np.where(np.isnan(a), a, np.where(np.isnan(b), b, np.where(b > a, b, a)))
+    return np.where(b > a, b, a)
+
+
+def merge_partials(a, b):
+    """The ``engine.partial_dtype`` records of the union of two disjoint
+    selections, elementwise (broadcast): sums and counts added (integer sums
+    wrap modulo 2^64 as NumPy's do), min and max NaN-propagating in the
+    records' own type; a side with ``count == 0`` is skipped, whatever its
+    other fields hold.  What ``moments.merge`` is to the other stats."""
+    a, b = np.asarray(a), np.asarray(b)
+    if a.dtype != b.dtype or a.dtype.names != ("sum", "count", "min", "max"):
+        raise ValueError(f"merge_partials: two arrays of one engine.partial_dtype. Got {a.dtype} and {b.dtype}")
+    a, b = np.broadcast_arrays(a, b)
+    out = np.zeros(a.shape, dtype=a.dtype)
+    with np.errstate(over="ignore", invalid="ignore"):
+        out["sum"] = a["sum"] + b["sum"]
+    out["count"] = a["count"] + b["count"]
+    out["min"] = _pmin(a["min"], b["min"])
+    out["max"] = _pmax(a["max"], b["max"])
+    ea, eb = a["count"] == 0, b["count"] == 0
+    out[eb] = a[eb]
+    only_b = ea & ~eb
+    out[only_b] = b[only_b]
+    return out
 
 
 def check_labels(labels, n: int, n_groups=None):
@@ -168,13 +208,28 @@ def chunk_lists(chunk_projs, chunks, labels, along: int, axes, final_shape, n_gr
                            out_off=out_off, order=order, seg=seg)
 
 
-def finalize(parts, stat: str, ddof: int = 0):
+def finalize(parts, stat: str, ddof: int = 0, dtype=None):
     """The result of a grouped query from its records: ``count`` the int64
     counts (never masked); ``mean`` a float64 masked array, masked where
     ``count == 0`` and NaN where a counted value is NaN or infinite; ``var`` /
-    ``std`` ``moments.finalize``: masked where ``count - ddof <= 0``."""
+    ``std`` ``moments.finalize``: masked where ``count - ddof <= 0``.
+    ``min`` / ``max`` / ``sum`` take ``engine.partial_dtype`` records and the
+    variable's ``dtype`` (None: the records' own 8-byte class): ``min`` and
+    ``max`` in the variable's dtype in native byte order, ``sum`` in
+    ``dtypes.sum_dtype`` (an f32 variable's f64 sum rounded once), each a
+    masked array with a full mask, masked (and 0) where ``count == 0``."""
     if stat not in STATS:
         raise ValueError(f"stat must be one of {STATS}. Got {stat!r}")
+    if stat in PARTIAL_STATS:
+        parts = np.asarray(parts)
+        if parts.dtype.names != ("sum", "count", "min", "max"):
+            raise ValueError(f"stat {stat!r} takes engine.partial_dtype records. Got {parts.dtype}")
+        vdt = parts.dtype[stat] if dtype is None else (sum_dtype(dtype) if stat == "sum" else native(dtype))
+        empty = parts["count"] == 0
+        with np.errstate(over="ignore"):   # (an f64 sum beyond f32 rounds to an infinity, as NumPy's f32 sum ends)
+            val = np.ascontiguousarray(parts[stat]).astype(vdt)
+        val[empty] = 0
+        return np.ma.MaskedArray(val, mask=empty)
     parts = np.asarray(parts, dtype=moments_dtype)
     if stat == "count":
         return np.ascontiguousarray(parts["count"], dtype=np.int64)

@@ -12,7 +12,15 @@ pyas_trend_cols + pyas_trend_finalize.  Whole queries: what the caller waits
 for, records back on the host included.  Median of --reps after 3 warm-up
 runs, in one process.
 
+--stat names the grouped statistics to time, comma-separated (default: mean,
+the output above unchanged).  Every other one ("max", "sum", "min") is timed
+in the same process and run, after the yardsticks: its whole queries
+(grouped_<stat>_<labels>) and its device chains, pyas_group_cols_partial alone
+(..._kernel_ms: the same bytes read and 32-byte records written as the mean's
+chain) and with the pyas_format_partials a query runs behind it (..._ms).
+
     python tools/bench_grouped.py [--reps 20] [--out profiles/grouped/bench_grouped.json]
+    python tools/bench_grouped.py --stat mean,max,sum --out profiles/grouped_extremes/bench_grouped.json
 """
 import argparse
 import json
@@ -42,9 +50,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=os.path.join("profiles", "grouped", "bench_grouped.json"))
+    ap.add_argument("--stat", default="mean",
+                    help="grouped statistics to time, comma-separated; mean is always timed (default: mean)")
     ap.add_argument("--chains-only", action="store_true",
                     help="the device chains alone (for a counter run): no whole query, nothing written")
     a = ap.parse_args()
+    a.extra = [s for s in dict.fromkeys(a.stat.split(",")) if s != "mean"]
+    if any(s not in ("min", "max", "sum") for s in a.extra):
+        ap.error("--stat takes mean, min, max and sum")
     import torch
     from pyactivestorage_amd.active import Active, attach_resident, release_resident
     from pyactivestorage_amd.synthetic import chunk_major_device
@@ -91,6 +104,10 @@ def main():
     for name, (lab, n_g) in vectors.items():
         cases.append(("grouped_" + name,
                       lambda lab=lab, n_g=n_g: act.grouped("mean", 0, lab, axis=(0,), n_groups=n_g)[...]))
+    for stat in a.extra:
+        for name, (lab, n_g) in vectors.items():
+            cases.append((f"grouped_{stat}_{name}", lambda stat=stat, lab=lab, n_g=n_g:
+                          act.grouped(stat, 0, lab, axis=(0,), n_groups=n_g)[...]))
     for name, fn in ([] if a.chains_only else cases):
         def run(name=name, fn=fn):
             last[name] = fn()
@@ -98,6 +115,8 @@ def main():
         print(json.dumps({name: q[name + "_ms"]}), flush=True)
     if not a.chains_only:
         spot_check(res, q, last, act, data, offsets, grid, cb, chunks, month, torch)
+        for stat in a.extra:
+            spot_check_stat(res, q, last, stat, data, offsets, grid, cb, chunks, month, torch)
     del last
     device_chains(res, a, vectors, data, offsets, grid, cb, chunks, shape, dt, attrs, coord, sync)
     release_resident(var)
@@ -129,6 +148,24 @@ def spot_check(res, q, last, act, data, offsets, grid, cb, chunks, month, torch)
     ok = (y != bench.FILL) & (y >= bench.VMIN) & (y <= bench.VMAX)
     ref = np.array([y[ok & (month == g)].mean() for g in range(12)])
     res["spot_check"]["column_5_7_max_abs_err"] = float(np.abs(np.ma.getdata(got)[:, 5, 7] - ref).max())
+
+
+def spot_check_stat(res, q, last, stat, data, offsets, grid, cb, chunks, month, torch):
+    """min / max / sum of column (5, 7) against NumPy, and the whole query against the mean's."""
+    q[f"grouped_{stat}_mod12_over_grouped_mod12"] = round(q[f"grouped_{stat}_mod12_ms"] / q["grouped_mod12_ms"], 3)
+    got = last[f"grouped_{stat}_mod12"]
+    col = data.view(torch.float32)
+    ys = []
+    for l in range(grid[0]):
+        o = int(offsets[l * grid[1] * grid[2]]) // 4
+        ys.append(col[o:o + cb // 4].view(*chunks)[:, 5, 7])
+    y = torch.cat(ys).cpu().numpy()
+    ok = (y != bench.FILL) & (y >= bench.VMIN) & (y <= bench.VMAX)
+    fn = {"min": np.min, "max": np.max, "sum": lambda v: np.sum(v.astype(np.float64))}[stat]
+    ref = np.array([fn(y[ok & (month == g)]) for g in range(12)])
+    res["spot_check"][f"{stat}_dtype"] = str(got.dtype)
+    res["spot_check"][f"{stat}_column_5_7_max_abs_err"] = float(np.abs(np.ma.getdata(got)[:, 5, 7].astype(np.float64)
+                                                                        - ref).max())
 
 
 def device_chains(res, a, vectors, data, offsets, grid, cb, chunks, shape, dt, attrs, coord, sync):
@@ -174,6 +211,24 @@ def device_chains(res, a, vectors, data, offsets, grid, cb, chunks, shape, dt, a
                                      rbuf.ptr + 8 * rows.n_rows, rows.n_rows, n_g, g, fin.ptr, st)
             ctx.synchronize(st)
         chains["grouped_" + name] = (chain, rows.n_rows, n_g)
+        for stat in a.extra:
+            vdt = engine.format_dtype(dt, stat)
+            val = DeviceBuffer(ctx, n_g * n_out * (vdt.itemsize + 1))
+            keep.append(val)
+
+            def kernel(rows=rows, rbuf=rbuf, fin=fin, n_g=n_g, sync_after=True):
+                assert engine.group_cols(ctx, plan.batch, plan.mask_up.struct, rbuf.ptr, rbuf.ptr + 4 * rows.n_rows,
+                                         rbuf.ptr + 8 * rows.n_rows, rows.n_rows, n_g, g, fin.ptr, st, partial=True)
+                if sync_after:
+                    ctx.synchronize(st)
+
+            def formatted(kernel=kernel, fin=fin, n_g=n_g, val=val, vdt=vdt, stat=stat):
+                kernel(sync_after=False)
+                engine.format_partials(ctx, dt, fin.ptr, n_g * n_out, stat, val.ptr,
+                                       val.ptr + n_g * n_out * vdt.itemsize, None, st)
+                ctx.synchronize(st)
+            chains[f"grouped_{stat}_{name}_kernel"] = (kernel, rows.n_rows, n_g)
+            chains[f"grouped_{stat}_{name}"] = (formatted, rows.n_rows, n_g)
     ctx.synchronize(st)
 
     def trend_chain():
@@ -199,6 +254,12 @@ def device_chains(res, a, vectors, data, offsets, grid, cb, chunks, shape, dt, a
     d["grouped_mod12_over_trend"] = round(d["grouped_mod12_ms"] / d["trend_ms"], 3)
     d["djf_over_mod12"] = round(d["grouped_djf_ms"] / d["grouped_mod12_ms"], 3)
     d["GBps_mean"] = round(n * cb / d["mean_ms"] / 1e6, 1)
+    for stat in a.extra:
+        for name in vectors:
+            for tail in ("", "_kernel"):
+                d[f"grouped_{stat}_{name}{tail}_over_grouped_{name}"] = round(
+                    d[f"grouped_{stat}_{name}{tail}_ms"] / d[f"grouped_{name}_ms"], 3)
+        d[f"{stat}_djf_over_mod12"] = round(d[f"grouped_{stat}_djf_kernel_ms"] / d[f"grouped_{stat}_mod12_kernel_ms"], 3)
     del keep
 
 
