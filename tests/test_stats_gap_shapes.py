@@ -110,10 +110,179 @@ def test_g4_ranks():
     assert sum(1 for s, c in zip(shape, chunks) if s % c) == 5
 
 
+# -- the cases of the trend and grouped modules ---------------------------------------
+ROOT = os.path.dirname(os.path.dirname(CSRC))
+K_TREND_ROFF = _const("kTrendRoff", _text("pyas_trend.hip"))
+K_TREND_ROWS = _const("kTrendRows", _text("pyas_internal.hpp"))
+K_TREND_V = _const("kTrendV", _text("pyas_internal.hpp"))
+K_GROUP_V = _const("kGroupV", _text("pyas_internal.hpp"))
+
+
+def test_group_rows_is_the_headers():
+    with open(os.path.join(ROOT, "include", "pyas.h")) as f:
+        m = re.search(r"#define\s+PYAS_GROUP_ROWS\s+(\d+)", f.read())
+    assert m and int(m.group(1)) == _lib.GROUP_ROWS
+    assert re.search(r"constexpr\s+int\s+kGroupRows\s*=\s*PYAS_GROUP_ROWS\s*;", _text("pyas_internal.hpp"))
+
+
+def test_dense_kernels_share_the_item_width_and_the_walks_the_launch_cap():
+    """G.dense_columns restates the launchers' items and bpc (pyas_trend_cols,
+    group_cols_run) from kTrendV / kGroupV and kBlock, read above; the C1 and
+    T2 checks below hold one width for the three kernels."""
+    capi = _text("pyas_capi.hip")
+    assert K_TREND_V == K_GROUP_V
+    for fn in ("pyas_trend_axes", "group_axes_run"):     # the walks' launches: LAUNCH_CAP workgroups a chunk
+        start = re.search(rf"^(static )?int {fn}\(", capi, re.M)
+        assert start, fn
+        body = capi[start.end():]
+        assert "axes_geometry(" in body[:re.search(r"^}", body, re.M).start()], fn
+
+
+def test_t1_reduced_positions_straddle_the_trend_map():
+    cap = K_TREND_ROFF
+
+    def n_reds(name, iname):
+        shape, chunks, axes, indexes, _ = G.case("T1", name)
+        return sorted({r for r, _ in G.chunk_counts(shape, chunks, indexes[iname], axes[0])})
+
+    for name, iname in (("row", "whole"), ("lane", "listed"), ("row-from", "from"), ("lane-from", "from")):
+        lo, hi = n_reds(name, iname)
+        assert lo <= cap < hi and hi == cap + 1, (name, lo, hi)      # the map and the walk in one launch
+        assert hi > 4 * K_WAVE                                        # the wave form's unrolled loop runs
+    assert n_reds("map", "whole") == [cap]
+    for name in ("row-from", "lane-from"):                            # non-zero starts in the walking chunk
+        index = G.index_of("T1", name, "from")
+        assert index[0].start > 0 and max(ix.start or 0 for ix in index[1:] if isinstance(ix, slice)) > 0
+    # the wave form needs the innermost dim reduced, the lane form kept; only the walk has the map
+    for name in G.T1:
+        row = 2 in G.case("T1", name)[2][0]
+        assert row == (not name.startswith("lane"))
+        walks = [r for r in G.runs("T1", name) if r[4] == "walk"]
+        assert walks and all(r[0] != "whole" or row for r in walks), name
+    assert {r[3] for r in G.runs("T1", "row")} == {0, 2}             # the coordinate along the innermost dim too
+
+
+def test_t2_rows_per_layer_exceed_and_equal_one_pass():
+    shape, chunks, axes, indexes, _ = G.case("T2", "rows")
+    assert G.layer_rows(shape, chunks, indexes["whole"], axes[0]) == [(K_TREND_ROWS + 37, 0), (K_TREND_ROWS, 0)]
+    assert G.layer_rows(shape, chunks, indexes["from37"], axes[0]) == [(K_TREND_ROWS, 37), (K_TREND_ROWS, 0)]
+    shape, chunks, axes, indexes, _ = G.case("T2", "p2")
+    rows = G.layer_rows(shape, chunks, indexes["whole"], axes[0])[0][0]
+    assert axes == [(0, 1)] and K_TREND_ROWS < rows < 2 * K_TREND_ROWS
+    assert K_TREND_ROWS % chunks[1]                                   # the pass boundary lies inside a row of dim 1
+    assert {r[3] for r in G.runs("T2", "p2")} == {0, 1}
+    # T1's lane case, whole, is dense too: two passes over two reduced dims
+    shape, chunks, axes, indexes, _ = G.case("T1", "lane")
+    assert G.layer_rows(shape, chunks, indexes["whole"], axes[0])[0][0] == 2 * K_TREND_ROWS + 1
+    for name in G.T2:
+        assert all(r[4] == "cols" for r in G.runs("T2", name))
+
+
+def test_c1_columns_take_several_workgroups():
+    for name, bpc in (("wg2", 2), ("wg3-4d", 3)):
+        shape, chunks, axes, indexes, _ = G.case("C1", name)
+        for iname, index in indexes.items():
+            cols = G.dense_columns(shape, chunks, index, axes[0], K_TREND_V, K_BLOCK)
+            assert {b for _, b in cols} == {bpc}, (name, iname)
+            assert any(n > K_BLOCK for n, _ in cols), (name, iname)                       # a later workgroup works
+            assert any(n > K_BLOCK and n % K_BLOCK for n, _ in cols), (name, iname)       # ... with idle lanes
+            assert any(n <= (b - 1) * K_BLOCK for n, b in cols), (name, iname)            # the early return
+        assert all(r[4] == "cols" for r in G.runs("C1", name))
+    shape, chunks, axes, indexes, _ = G.case("C1", "wg2")
+    whole = G.dense_columns(shape, chunks, indexes["whole"], axes[0], K_TREND_V, K_BLOCK)
+    box = G.dense_columns(shape, chunks, indexes["box"], axes[0], K_TREND_V, K_BLOCK)
+    assert whole[0][0] == 270 and box[0][0] == 240 and box[2][0] == 270   # a cut first column, dead lanes in its first workgroup
+    shape, chunks, axes, _, _ = G.case("C1", "wg3-4d")
+    assert len(shape) - 1 - len(axes[0]) == 1                        # a kept dim between the prefix and the innermost
+    # the G2 variables, whole, are dense as well
+    shape, chunks, _, _, _ = G.case("G2", "one")
+    assert G.dense_columns(shape, chunks, G.ALL, (0,), K_TREND_V, K_BLOCK) == [(130 * 33, 17)]
+
+
+def test_g2_walk_records_exceed_one_trip():
+    per_trip = G.LAUNCH_CAP * K_BLOCK
+    for name in G.G2:
+        shape, chunks, _, _, _ = G.case("G2", name)
+        walk = [r for r in G.runs("G2", name) if r[4] == "walk"]
+        assert len(walk) == 1 and walk[0][2] == (0,) and walk[0][3] == 0
+        for n_red, n_keep in G.chunk_counts(shape, chunks, walk[0][1], (0,)):
+            assert n_red == 3 and per_trip < n_keep <= 2 * per_trip       # k_trend_axes: a second trip
+            # k_group_axes under [0, 1, 0]: two local groups, three trips, group 1 wholly past the first
+            assert 2 * per_trip < 2 * n_keep <= 3 * per_trip and n_keep >= G.G2_SECOND_TRIP
+
+
+def _gap_runs():
+    for group in ("T1", "T2", "C1", "G2", "G3", "G4", "G5"):
+        for name in G.GROUPS[group]:
+            if (group, name) == ("G3", "runs"):
+                continue
+            dts = {"G3": G.G3_DTYPES, "G5": G.G5_DTYPES, **G.T_DTYPES}.get(group, ["<f4"])
+            for dt in dts:
+                yield pytest.param(group, name, dt, id=f"{group}-{name}-{dt[1:]}{'be' if dt[0] == '>' else ''}")
+
+
+# outputs of two elements: one masked element leaves no slope (NaN on both sides)
+FEW_POINTS = {("G4", "8d", "strided", (0,))}
+
+
+@pytest.mark.parametrize("group,name,dt", list(_gap_runs()))
+def test_runs_are_well_posed(group, name, dt):
+    """Every run of the trend and grouped modules: a masked case masks
+    something but not everything, and every output keeps valid elements at
+    two positions or more along the coordinate's dim."""
+    nd = len(G.case(group, name)[0])
+    for masked in (False, True):
+        x, ax = G.single(group, name, dt, masked)
+        m = np.ma.getmaskarray(G.masked_selection(x, ax, G.ALL))
+        assert m.any() == masked and not m.all()
+        for iname, index, axis, along, path in G.runs(group, name):
+            assert along in (axis if axis is not None else range(nd))
+            assert path == ("cols" if iname in ("whole", "from1", "from37", "box") and G.is_prefix(axis, nd) else "walk")
+            sel = m[index]
+            assert sel.any() == masked and not sel.all()
+            points = G.trend_points(m, index, axis, along)
+            assert points >= 2 or (masked and (group, name, iname, axis) in FEW_POINTS), (iname, axis, along, points)
+        # the padding against the valid data (see G.pad_of): beyond them, but for G5's full-range integers
+        valid = x[~m].astype(np.float64)
+        pad = float(G.pad_of(dt))
+        assert pad > valid.max() or (group == "G5" and np.dtype(dt).kind in "iu" and pad == valid.max()), (masked, pad)
+        if not masked or np.dtype(dt).kind != "u":      # (an unsigned fill value is the padding itself)
+            assert not np.ma.getmaskarray(G.masked_selection(np.array([G.pad_of(dt)], np.dtype(dt)), ax, G.ALL)).any()
+
+
+@pytest.mark.parametrize("mode", G.M_MODES)
+@pytest.mark.parametrize("dt", G.M_DTYPES)
+def test_mask_cases_are_well_posed(dt, mode):
+    from pyactivestorage_amd.variable import get_missing_attributes
+    x, attrs, pad, plants = G.mask_case(dt, mode)
+    fill, miss, lo, hi = get_missing_attributes(attrs)
+    assert [v is not None for v in (fill, miss, lo, hi)] == {"both": [True] * 4, "missing": [False, True, False, False],
+                                                            "max": [False, False, False, True]}[mode]
+    if mode == "both":
+        assert lo < fill < hi and lo < miss < hi                      # no rule is trimmed away
+    m = np.ma.getmaskarray(G.masked_selection(x, attrs, G.ALL))
+    for v, want in plants.items():
+        hit = x == np.dtype(dt).type(v)
+        assert hit.sum() >= 5 and (m[hit] == want).all(), (v, want)
+    assert not np.ma.getmaskarray(G.masked_selection(np.array([pad]), attrs, G.ALL)).any()   # padding read would count
+    assert mode != "missing" or pad > x.max()       # ... and without a valid_max it would be a max as well
+    for index in G.M_INDEXES.values():
+        index = G.per_dim(index, 3)
+        assert m[index].any() and G.trend_points(m, index, (0,), 0) >= 2
+
+
+def test_g6d_offsets_miss_and_keep_the_alignment():
+    assert G.G6D_SHAPE[-1] % K_TREND_V == 0        # (so every byte plane of the shuffled chunk starts 4-aligned too)
+    for dt, shuffled, off, vec in G.G6D_CASES:
+        assert (off % G.k_align(dt, shuffled, K_TREND_V) == 0) == vec and 0 < off < 16
+        assert shuffled or off % np.dtype(dt).itemsize == 0
+    assert {(dt, sh) for dt, sh, _, vec in G.G6D_CASES if vec} == {("<f4", True)}
+
+
 def _cases():
     for group, cases in G.GROUPS.items():
         for name in cases:
-            dts = {"G3": G.G3_DTYPES, "G5": G.G5_DTYPES}.get(group, ["<f4"])
+            dts = {"G3": G.G3_DTYPES, "G5": G.G5_DTYPES, **G.T_DTYPES}.get(group, ["<f4"])
             for dt in dts:
                 yield pytest.param(group, name, dt, id=f"{group}-{name}-{dt[1:]}{'be' if dt[0] == '>' else ''}")
 
