@@ -646,6 +646,91 @@ enum { PYAS_TREND_SLOPE = 0, PYAS_TREND_INTERCEPT = 1 };
 int pyas_trend_finalize(pyas_ctx *ctx, const pyas_comoments *in, int64_t n, int32_t what,
                         double *value, uint8_t *masked, void *stream);
 
+/* ---- spells past a threshold (Active.spell) -----------------------------------
+ * Partial record of the runs of true elements in a sequence of selected
+ * positions along one dim (40 bytes, ten int32).  A position is true when its
+ * element is unmasked and float64(x) op threshold holds (values convert as
+ * astype(float64) does; a NaN compares false but counts as unmasked); a masked
+ * element is false.  A run is a maximal sequence of consecutive true positions.
+ *   n, n_true   unmasked / true positions
+ *   len         positions covered
+ *   head, tail  length of the leading / trailing run (both == len when every
+ *               position is true)
+ *   best        longest run anywhere
+ *   days, events  total length / number of the interior runs of length >=
+ *               min_length (an interior run touches neither end of the sequence)
+ *   min_length  the query's L (0 in the zero record)
+ * The all-zero record is neutral.  Unlike the other records this one merges in
+ * sequence order only: merged(a, b) with a's positions before b's,
+ *   L = max(a.min_length, b.min_length); a_all = a.head == a.len; b_all likewise
+ *   n, n_true, len add
+ *   head = a_all ? a.len + b.head : a.head;  tail = b_all ? b.len + a.tail : b.tail
+ *   j = a.tail + b.head;  best = max(a.best, b.best, j)
+ *   days, events add; and when !a_all && !b_all && j >= L: days += j, events += 1
+ * is associative but not commutative.  Every combine of the library folds its
+ * records sequentially in a fixed order (a segment in index order, chunk layers
+ * in C order over the reduced dim's chunk coordinates), so the caller hands
+ * the records over in sequence order and nothing else is needed.  Finalize:
+ *   longest = best
+ *   events += (head >= L && head > 0) + (head != len && tail >= L && tail > 0)
+ *   days   += (head >= L ? head : 0) + (head != len && tail >= L ? tail : 0)
+ * All counts are int32: a sequence holds fewer than 2^31 positions. */
+typedef struct {
+    int32_t n, n_true, len, head, tail, best, days, events, min_length, reserved;
+} pyas_spell;
+
+enum { PYAS_SPELL_GT = 0, PYAS_SPELL_GE = 1, PYAS_SPELL_LT = 2, PYAS_SPELL_LE = 3 };
+enum { PYAS_SPELL_LONGEST = 0, PYAS_SPELL_DAYS = 1, PYAS_SPELL_EVENTS = 2 };
+typedef struct {
+    int32_t dim;             /* the chunk dim the runs follow: the one reduced dim */
+    int32_t op;              /* PYAS_SPELL_GT / GE / LT / LE */
+    int32_t min_length;      /* L >= 1 */
+    double threshold;        /* finite */
+} pyas_spell_rule;
+
+/* pyas_moments_axes for spell records: out[out_offsets[c] + o] receives the
+ * record of output o (C order over the kept selected dims) of chunk c, over the
+ * chunk's selected positions along rule->dim in selection order (a slice by
+ * its step, an index list in list order: the host passes increasing lists).
+ * axes_mask must be 1u << rule->dim; op must be one of the four and
+ * min_length >= 1 (PYAS_EINVAL otherwise, and when rule is NULL).  out_offsets
+ * may be NULL only for a 1-D variable (chunk c's record at out[c]).  When
+ * rule->dim is the innermost dim a wave owns an output and takes 64
+ * consecutive positions per step (two ballots and bit operations give the
+ * word's record, merged into the wave's in word order); otherwise a lane walks
+ * its output's positions in order.  A per-element walk for any selection and
+ * mask: it has no speed target.  Other errors as pyas_moments_axes. */
+int pyas_spell_axes(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask,
+                    const pyas_spell_rule *rule, uint32_t axes_mask, const int64_t *out_offsets,
+                    pyas_spell *out, void *stream);
+/* The dense path of a box query: pyas_spell_axes + pyas_spell_combine_grid in
+ * ONE launch that writes one finished record per final output (out, device, C
+ * order over grid->out_extent) and no per-chunk records.  The caller's promises
+ * and the grid fields read are those of pyas_trend_cols.  rule->dim must be 0,
+ * the single reduced dim (grid->axes_mask == 1), with at least one kept dim
+ * behind it, and the mask must have no vector tables: otherwise PYAS_ENOTSUP,
+ * nothing is launched and the caller takes pyas_spell_axes.  A lane owns 4
+ * consecutive outputs along the innermost dim and walks them through every row
+ * of every chunk layer in increasing index order, keeping the current run, the
+ * head and the counts in integer registers, so a record is the lane's own
+ * (nothing is merged) and equals the two-step path's exactly. */
+int pyas_spell_cols(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask,
+                    const pyas_spell_rule *rule, const pyas_grid *grid, pyas_spell *out,
+                    void *stream);
+/* pyas_moments_combine_segments / pyas_moments_combine_grid for spell records
+ * (same orders, same errors).  The records of a segment must be listed, and
+ * the chunk layers must lie, in sequence order. */
+int pyas_spell_combine_segments(pyas_ctx *ctx, const pyas_spell *in, const int64_t *index,
+                                const int64_t *seg_offsets, int64_t n_segments,
+                                pyas_spell *out, void *stream);
+int pyas_spell_combine_grid(pyas_ctx *ctx, const pyas_spell *in, const pyas_grid *grid,
+                            pyas_spell *out, void *stream);
+/* value[i] = the finalized longest / days / events (stat: PYAS_SPELL_*) of
+ * record i as int32, masked[i] = (n == 0), all device: 5 bytes per output cross
+ * PCIe instead of 40.  A masked value is 0. */
+int pyas_spell_finalize(pyas_ctx *ctx, const pyas_spell *in, int64_t n, int32_t stat,
+                        int32_t *value, uint8_t *masked, void *stream);
+
 /* ---- per-label second moments (Active.grouped) -------------------------------
  * The pyas_moments record, one per (output, group): an element whose global
  * index along one reduced dim is i belongs to group labels[i] >= 0, or to no

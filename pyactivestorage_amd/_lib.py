@@ -68,6 +68,22 @@ class Coord(ctypes.Structure):
 TREND_SLOPE, TREND_INTERCEPT = 0, 1
 
 
+class Spell(ctypes.Structure):
+    """pyas_spell: the runs of true positions of a sequence (merged in sequence order only)."""
+    _fields_ = [(name, ctypes.c_int32) for name in ("n", "n_true", "len", "head", "tail", "best", "days", "events",
+                                                    "min_length", "reserved")]
+
+
+class SpellRule(ctypes.Structure):
+    """pyas_spell_rule: the dim the runs follow, the comparison, the threshold and the minimum run length."""
+    _fields_ = [("dim", ctypes.c_int32), ("op", ctypes.c_int32), ("min_length", ctypes.c_int32),
+                ("threshold", ctypes.c_double)]
+
+
+SPELL_OPS = {"gt": 0, "ge": 1, "lt": 2, "le": 3}              # PYAS_SPELL_GT .. PYAS_SPELL_LE
+SPELL_STATS = {"longest": 0, "days": 1, "events": 2}          # PYAS_SPELL_LONGEST .. PYAS_SPELL_EVENTS
+
+
 class GroupRows(ctypes.Structure):
     """pyas_group_rows: the sorted reduced rows of a box query (device pointers) and the group count."""
     _fields_ = [("layer", ctypes.c_void_p), ("offset", ctypes.c_void_p), ("label", ctypes.c_void_p),
@@ -213,6 +229,8 @@ COMOMENTS_NBYTES = ctypes.sizeof(Comoments)
 assert COMOMENTS_NBYTES == 48
 WSUM_NBYTES = ctypes.sizeof(Wsum)
 assert WSUM_NBYTES == 32
+SPELL_NBYTES = ctypes.sizeof(Spell)
+assert SPELL_NBYTES == 40
 
 _vp = ctypes.c_void_p
 _i32 = ctypes.c_int32
@@ -278,6 +296,13 @@ SIGNATURES = {
     "pyas_trend_cols": [_vp, ctypes.POINTER(Batch), ctypes.POINTER(Mask), ctypes.POINTER(Coord),
                         ctypes.POINTER(Grid), _vp, _vp],
     "pyas_trend_finalize": [_vp, _vp, _i64, _i32, _vp, _vp, _vp],
+    "pyas_spell_axes": [_vp, ctypes.POINTER(Batch), ctypes.POINTER(Mask), ctypes.POINTER(SpellRule), _u32, _vp, _vp,
+                        _vp],
+    "pyas_spell_cols": [_vp, ctypes.POINTER(Batch), ctypes.POINTER(Mask), ctypes.POINTER(SpellRule),
+                        ctypes.POINTER(Grid), _vp, _vp],
+    "pyas_spell_combine_segments": [_vp, _vp, _vp, _vp, _i64, _vp, _vp],
+    "pyas_spell_combine_grid": [_vp, _vp, ctypes.POINTER(Grid), _vp, _vp],
+    "pyas_spell_finalize": [_vp, _vp, _i64, _i32, _vp, _vp, _vp],
     "pyas_group_cols": [_vp, ctypes.POINTER(Batch), ctypes.POINTER(Mask), ctypes.POINTER(GroupRows),
                         ctypes.POINTER(Grid), _vp, _vp],
     "pyas_group_axes": [_vp, ctypes.POINTER(Batch), ctypes.POINTER(Mask), ctypes.POINTER(GroupLists), _u32, _vp, _vp,

@@ -52,11 +52,12 @@ import warnings
 
 import numpy as np
 
-from . import _lib, comoments, engine, grouped, histogram, moments, quantile, selection, trend, weighted, zerosign
+from . import _lib, comoments, engine, grouped, histogram, moments, quantile, selection, spell, trend, weighted, \
+    zerosign
 from .batch import ReductionPlan, _all_full
 from .device import DeviceBuffer, get_context
 from .dtypes import native, sum_dtype
-from .indexing import OrthogonalIndexer
+from .indexing import OrthogonalIndexer, _normalize
 from .ingest import read_ranges, read_ranges_zlib
 from .inflate import InflateBatch, is_zlib, pack_streams
 from .masking import compile_missing
@@ -411,6 +412,8 @@ class Active:
         self._trend_path = None         # the last trend query: "cols" (dense column kernel) or "walk"
         self._grouped = None            # grouped: {"stat", "along", "labels", "n_groups"} of the next query
         self._grouped_path = None       # the last grouped query: "cols" (dense column kernel) or "walk"
+        self._spell = None              # spell: {"along", "op", "threshold", "stat", "min_length"} of the next query
+        self._spell_path = None         # the last spell query: "cols" (dense column kernel) or "walk"
         self._select_stats = None       # the last quantile query: its digit width, count launches and chains
         self._max_threads = int(max_threads)
         self.device = device
@@ -457,6 +460,15 @@ class Active:
         self._co = None
         self._trend = None
         self._grouped = None
+        self._spell = None
+
+    @property
+    def spell_path(self):
+        """Which kernel the last :meth:`spell` query ran: ``"cols"`` (the dense
+        column walk, pyas_spell_cols) or ``"walk"`` (the per-element walk,
+        pyas_spell_axes); None before the first one and after a query that
+        reached no kernel (an empty selection)."""
+        return self._spell_path
 
     @property
     def grouped_path(self):
@@ -616,6 +628,47 @@ class Active:
             self._axis = axis
         return self
 
+    def spell(self, along, op, threshold, stat="longest", min_length=1):
+        """Spells past a threshold along one dimension, per output, in one
+        pass on the device.  An element is *true* when it is selected,
+        unmasked and ``float64(x) op threshold`` holds (``op``: ``"gt"``,
+        ``"ge"``, ``"lt"`` or ``"le"``; ``threshold``: a finite number; a NaN
+        compares false but counts as unmasked; a masked element is false).  A
+        run is a maximal sequence of true elements that are consecutive in the
+        selection along ``along`` (with ``[::3]``, consecutive selected
+        elements).  ``stat``: ``"longest"``, the longest run (CDD, CWD);
+        ``"days"``, the total length of the runs of at least ``min_length``
+        (WSDI, CSDI); ``"events"``, the number of such runs.  ``along``: an
+        int in ``[-ndim, ndim)``; it becomes the only reduced axis, so the
+        query returns an int64 masked array of the shape
+        ``mean(axis=(along,))`` returns, masked where an output has no
+        unmasked element.  With ``components`` a dict of the record's fields
+        (``n``, ``n_true``, ``len``, ``head``, ``tail``, ``best``, ``days``,
+        ``events``, ``min_length``: see :mod:`.spell`) and ``longest``,
+        ``days_total`` and ``events_total`` finalized, so ``spell.merge`` joins
+        the components of selections that follow each other along ``along``
+        (years, files) and ``spell.finalize`` reads the result.  The selection
+        along ``along`` must be a slice of step >= 1, a strictly increasing
+        index list or a boolean mask (ValueError otherwise) of fewer than 2^31
+        positions.  A unit-step box query with ``along=0`` and a dimension
+        behind it runs the dense column kernel (pyas_spell_cols), anything
+        else the per-element walk (pyas_spell_axes): see :attr:`spell_path`;
+        both give the same integers.  The settings hold for one query."""
+        ndim = self.ds.ndim
+        if isinstance(along, (bool, np.bool_)) or not isinstance(along, (int, np.integer)) \
+                or not -ndim <= along < ndim:
+            raise ValueError(f"spell: along={along!r} is out of range for {ndim} dimensions")
+        d = int(along) % ndim
+        try:
+            settings = {"along": d, "op": spell.check_op(op), "threshold": spell.check_threshold(threshold),
+                        "stat": spell.check_stat(stat), "min_length": spell.check_min_length(min_length)}
+        except ValueError as exc:
+            raise ValueError(f"spell: {exc}") from None
+        self._spell = settings
+        self._method = "spell"
+        self._axis = (d,)
+        return self
+
     def grouped(self, stat, along, labels, axis=None, ddof=0, n_groups=None):
         """One statistic per label along a reduced dimension, in one pass on
         the device: ``stat`` (``"mean"``, ``"var"``, ``"std"``, ``"count"``,
@@ -761,6 +814,7 @@ class Active:
             self._co = None              # and a cov / corr's second variable
             self._trend = None           # and a trend's coordinate
             self._grouped = None         # and a grouped query's labels
+            self._spell = None           # and a spell's threshold
             for store in held:
                 _unhold(store)
             self._held.stores = []
@@ -790,6 +844,9 @@ class Active:
         gr = self._method == "grouped"
         if gr and self.group is not None:
             raise NotImplementedError("grouped with group=…: second moments are reduced on one GPU only")
+        sp = self._method == "spell"
+        if sp and self.group is not None:
+            raise NotImplementedError("spell with group=…: spell records are reduced on one GPU only")
         if self._axis is None:
             self._axis = tuple(range(ds.ndim))
         elif isinstance(self._axis, int):
@@ -801,10 +858,10 @@ class Active:
             raise ValueError(f"grouped: along={self._grouped['along']} is not among the reduced axes "
                              f"{self._norm_axes()}: every output would hold one label")
         cache_key = None
-        # (var / std, weighted, histogram, quantile, cov / corr, trend and grouped queries bypass the plan cache: its
-        # plans replay pyas_partial launches)
+        # (var / std, weighted, histogram, quantile, cov / corr, trend, grouped and spell queries bypass the plan
+        # cache: its plans replay pyas_partial launches)
         if self.resident and self.group is None and self._method is not None and not second and not has_w \
-                and not hist and not quant and not co and not tr and not gr:
+                and not hist and not quant and not co and not tr and not gr and not sp:
             ikey = _index_key(index)
             if ikey is not None:
                 cache_key = (ikey, self._norm_axes(), _missing_key(self.missing))
@@ -813,6 +870,8 @@ class Active:
                     return hit
         compressor, filters = (None, None) if not ds.filter_pipeline else \
             decode_filters(ds.filter_pipeline, ds.dtype.itemsize, ds.name)
+        if sp:
+            self._check_spell_index(index)
         indexer = OrthogonalIndexer(index, ds.shape, ds.chunks)
         if self.components and self._method is None:       # active.py:483-485
             raise ValueError("Setting components to True for None statistical method.")
@@ -836,6 +895,8 @@ class Active:
             return self._reduce_trend(indexer, compressor, filters, self._norm_axes())
         if gr:
             return self._reduce_grouped(indexer, compressor, filters, self._norm_axes())
+        if sp:
+            return self._reduce_spell(indexer, compressor, filters)
         return self._reduce(indexer, compressor, filters, self._norm_axes(), cache_key)
 
     def _norm_axes(self):
@@ -1449,6 +1510,95 @@ class Active:
                 np.ma.MaskedArray(intercept, mask=empty)
             return out
         return trend.slope(parts)
+
+    # -- spell -------------------------------------------------------------------
+    def _check_spell_index(self, index):
+        """The index along the spell dimension keeps the elements in order: a
+        slice of step >= 1, a strictly increasing index list or a boolean
+        mask.  ValueError otherwise (what no statistic accepts is left to the
+        planner's own errors)."""
+        d = self._spell["along"]
+        s = _normalize(index, self.ds.ndim)[d]
+        if isinstance(s, slice):
+            if isinstance(s.step, (int, np.integer)) and s.step < 1:
+                raise ValueError(f"spell: the slice along dimension {d} has step {s.step}; runs follow the "
+                                 "selection in increasing order, so the step must be >= 1")
+            return
+        if isinstance(s, (list, np.ndarray)) and np.ndim(s) > 0:
+            a = np.asarray(s)
+            if a.ndim == 1 and a.dtype.kind in "iu":
+                a = np.where(a < 0, a.astype(np.int64) + self.ds.shape[d], a.astype(np.int64))
+                if a.size > 1 and not bool(np.all(np.diff(a) > 0)):
+                    raise ValueError(f"spell: the index list along dimension {d} must be strictly increasing "
+                                     "(no repeats): runs follow the selection in order")
+            return
+        raise ValueError(f"spell: the index along dimension {d} must be a slice, an increasing index list or a "
+                         f"boolean mask. Got {s!r}")
+
+    def _reduce_spell(self, indexer, compressor, filters):
+        """spell: records of the runs along the one reduced axis.  A unit-step
+        box query with ``along == 0`` and a dim behind it takes the dense
+        column kernel (pyas_spell_cols: one finished record per output, the
+        chunk layers walked in the kernel); anything else per-chunk records
+        (pyas_spell_axes) merged in the orders of :meth:`_reduce_records`,
+        each of which folds the chunks of an output in increasing chunk order
+        along the axis.  The statistic and its mask are computed on the device
+        (pyas_spell_finalize) unless ``components`` is set."""
+        ds = self.ds
+        sp = self._spell
+        along, axes = sp["along"], (sp["along"],)
+        self._spell_path = None
+        if indexer.dim_indexers[along].nitems >= 2 ** 31:
+            raise NotImplementedError(f"spell: {indexer.dim_indexers[along].nitems} selected positions along "
+                                      f"dimension {along}; the record counts in int32 (fewer than 2^31)")
+        q = self._query_plan(indexer, compressor, filters, axes)
+        final_shape, n_final = q.final_shape, q.n_final
+        if q.empty:
+            return self._format_spell(np.zeros(final_shape, dtype=engine.spell_dtype))
+        ctx, st, plan = q.ctx, q.st, q.plan
+        rule = (along, sp["op"], sp["threshold"], sp["min_length"])
+        fin = DeviceBuffer(ctx, n_final * _lib.SPELL_NBYTES)
+
+        def launch(off_ptr, out_ptr):
+            engine.spell_axes(ctx, plan.batch, plan.mask_up.struct, *rule, off_ptr, out_ptr, st)
+        # the dense path: every dim one unit-step range, axis 0 reduced, a kept dim behind it
+        dense = q.dims is not None and axes == (0,) and ds.ndim > 1 and bool(np.all(q.table[:, :ds.ndim, 1] == 1))
+        done = False
+        if dense:
+            g = _grid_struct(ds.ndim, axes, final_shape, {"n_coords": [len(p) for p in q.dims]}, None, None)
+            done = engine.spell_cols(ctx, plan.batch, plan.mask_up.struct, *rule, g, fin.ptr, st)
+        keep = []
+        if not done:
+            fin, keep = self._reduce_records(q, axes, _lib.SPELL_NBYTES, launch, engine.spell_combine_segments,
+                                             engine.spell_combine_grid, fin=fin)
+        self._spell_path = "cols" if done else "walk"
+        if self._components:
+            final = self._records_back(q, fin, keep, engine.spell_dtype)
+            del keep
+            return self._format_spell(final)
+        # the statistic and its mask on the device: 5 bytes per output come back
+        vbuf = DeviceBuffer(ctx, n_final * 5)
+        engine.spell_finalize(ctx, fin.ptr, n_final, sp["stat"], vbuf.ptr, vbuf.ptr + 4 * n_final, st)
+        val = np.empty(n_final, dtype=np.int32)
+        msk = np.empty(n_final, dtype=np.uint8)
+        ctx.d2h(val, vbuf.ptr, st)
+        ctx.d2h(msk, vbuf.ptr + 4 * n_final, st)
+        ctx.synchronize(st)
+        del keep
+        return np.ma.MaskedArray(val.reshape(final_shape).astype(np.int64), mask=msk.reshape(final_shape).astype(bool))
+
+    def _format_spell(self, parts):
+        """The int64 result of a spell query from its combined records on the
+        host (spell.finalize), or its components: the record's fields, and the
+        three statistics finalized."""
+        if self._components:
+            out = {name: np.ma.MaskedArray(np.ascontiguousarray(parts[name]).astype(np.int64),
+                                           mask=np.zeros(parts.shape, dtype=bool)) for name in spell.FIELDS}
+            out["longest"] = spell.finalize(parts, "longest")
+            out["days_total"] = spell.finalize(parts, "days")
+            out["events_total"] = spell.finalize(parts, "events")
+            return out
+        return spell.finalize(parts, self._spell["stat"])
 
     # -- grouped -----------------------------------------------------------------
     def _reduce_grouped(self, indexer, compressor, filters, axes):

@@ -361,6 +361,40 @@ hipError_t launch_trend_axes(int dtype, const TrendArgs &a, int64_t grid, hipStr
 hipError_t launch_trend_cols(int dtype, const TrendColsArgs &a, bool shuf, int64_t grid, hipStream_t st);
 hipError_t launch_trend_finalize(const pyas_comoments *in, int64_t n, int32_t what, double *value, uint8_t *masked,
                                  hipStream_t st);
+// spells past a threshold (pyas_spell.hip): pyas_spell records, merged in sequence order
+struct SpellTest {
+    double threshold;                 // as the kernel compares: negated for lt / le
+    int32_t min_length;
+    bool neg, incl;                   // lt / le: compare -x > -threshold; ge / le: equality counts
+};
+struct SpellArgs {
+    ReduceArgs r;                     // r.out unused
+    int32_t dim;                      // the one reduced dim
+    int64_t bpc;                      // workgroups per chunk
+    const int64_t *out_offsets;       // NULL (1-D variables only): chunk c's record at out[c]
+    pyas_spell *out;
+    SpellTest t;
+    bool shuf, bswap;
+    bool row;                         // dim is the innermost dim: a wave per output
+};
+struct SpellColsArgs {
+    ReduceArgs r;                     // r.out unused; r.sel NULL: whole chunks
+    int64_t n_coords[PYAS_MAX_DIMS];  // chunk coordinates per dim (chunk n = C-order position)
+    int64_t ostride[PYAS_MAX_DIMS];   // final-output element strides (kept dims)
+    int64_t n_layers, n_cols;         // chunks along dim 0 / the kept dims
+    int64_t bpc;                      // workgroups per column
+    pyas_spell *out;                  // one finished record per final output
+    SpellTest t;
+    bool bswap, masked;
+};
+hipError_t launch_spell_axes(int dtype, const SpellArgs &a, int64_t grid, hipStream_t st);
+hipError_t launch_spell_cols(int dtype, const SpellColsArgs &a, bool shuf, int64_t grid, hipStream_t st);
+hipError_t launch_spell_segments(const pyas_spell *in, const int64_t *index, const int64_t *seg, int64_t n_seg,
+                                 pyas_spell *out, hipStream_t st);
+hipError_t launch_spell_grid(const pyas_spell *in, const pyas_grid &g, int64_t n_out, int64_t n_layers,
+                             pyas_spell *out, hipStream_t st);
+hipError_t launch_spell_finalize(const pyas_spell *in, int64_t n, int32_t stat, int32_t *value, uint8_t *masked,
+                                 hipStream_t st);
 // per-label second moments (pyas_grouped.hip): pyas_moments records, one per (output, group)
 constexpr int kGroupV = 4;            // k_group_cols: consecutive outputs per lane
 constexpr int kGroupRows = PYAS_GROUP_ROWS;   // k_group_cols: rows of the sorted list staged in LDS per pass (16 KiB)

@@ -31,6 +31,10 @@ moments_dtype = np.dtype([("count", "<i8"), ("mean", "<f8"), ("m2", "<f8"), ("re
 comoments_dtype = np.dtype([("count", "<i8"), ("mean_x", "<f8"), ("mean_y", "<f8"), ("m2_x", "<f8"),
                             ("m2_y", "<f8"), ("cxy", "<f8")])
 
+# Host view of ``pyas_spell``
+spell_dtype = np.dtype([(name, "<i4") for name in ("n", "n_true", "len", "head", "tail", "best", "days", "events",
+                                                   "min_length", "reserved")])
+
 # Host view of ``pyas_wsum``
 wsum_dtype = np.dtype([("count", "<i8"), ("sw", "<f8"), ("swx", "<f8"), ("reserved", "<u8")])
 
@@ -291,6 +295,52 @@ def trend_finalize(ctx: Context, in_ptr, n: int, what: int, value_ptr, mask_ptr,
     records as float64 values and mask bytes, on the device."""
     _lib.check(ctx.lib.pyas_trend_finalize(ctx.handle, in_ptr, int(n), int(what), value_ptr, mask_ptr, stream),
                "pyas_trend_finalize")
+
+
+def _spell_rule(dim: int, op: str, threshold: float, min_length: int) -> _lib.SpellRule:
+    return _lib.SpellRule(int(dim), _lib.SPELL_OPS[op], int(min_length), float(threshold))
+
+
+def spell_axes(ctx: Context, batch: _lib.Batch, mask: _lib.Mask, dim: int, op: str, threshold: float,
+               min_length: int, out_offsets_ptr, out_ptr, stream) -> None:
+    """pyas_spell_axes: spell records along chunk dim ``dim`` (the one reduced
+    dim) per chunk output, laid out like :func:`moments_axes`'."""
+    rule = _spell_rule(dim, op, threshold, min_length)
+    _lib.check(ctx.lib.pyas_spell_axes(ctx.handle, ctypes.byref(batch), ctypes.byref(mask), ctypes.byref(rule),
+                                       1 << int(dim), out_offsets_ptr, out_ptr, stream), "pyas_spell_axes")
+
+
+def spell_cols(ctx: Context, batch: _lib.Batch, mask: _lib.Mask, dim: int, op: str, threshold: float,
+               min_length: int, grid: _lib.Grid, out_ptr, stream) -> bool:
+    """pyas_spell_cols: one finished record per final output of a unit-step
+    box query, in one launch.  False (nothing launched) when the geometry is
+    not the dense path's (PYAS_ENOTSUP): the caller runs :func:`spell_axes`."""
+    rule = _spell_rule(dim, op, threshold, min_length)
+    rc = ctx.lib.pyas_spell_cols(ctx.handle, ctypes.byref(batch), ctypes.byref(mask), ctypes.byref(rule),
+                                 ctypes.byref(grid), out_ptr, stream)
+    if rc == _lib.ENOTSUP:
+        return False
+    _lib.check(rc, "pyas_spell_cols")
+    return True
+
+
+def spell_combine_segments(ctx: Context, in_ptr, index_ptr, seg_ptr, n_seg, out_ptr, stream) -> None:
+    """pyas_spell_combine_segments (``index_ptr`` None: the identity); the
+    records of a segment in sequence order."""
+    _lib.check(ctx.lib.pyas_spell_combine_segments(ctx.handle, in_ptr, index_ptr, seg_ptr, int(n_seg), out_ptr,
+                                                   stream), "pyas_spell_combine_segments")
+
+
+def spell_combine_grid(ctx: Context, in_ptr, grid: _lib.Grid, out_ptr, stream) -> None:
+    _lib.check(ctx.lib.pyas_spell_combine_grid(ctx.handle, in_ptr, ctypes.byref(grid), out_ptr, stream),
+               "pyas_spell_combine_grid")
+
+
+def spell_finalize(ctx: Context, in_ptr, n: int, stat: str, value_ptr, mask_ptr, stream) -> None:
+    """pyas_spell_finalize: ``stat`` (``longest``, ``days`` or ``events``) of
+    ``n`` records as int32 values and mask bytes, on the device."""
+    _lib.check(ctx.lib.pyas_spell_finalize(ctx.handle, in_ptr, int(n), _lib.SPELL_STATS[stat], value_ptr, mask_ptr,
+                                           stream), "pyas_spell_finalize")
 
 
 def group_cols(ctx: Context, batch: _lib.Batch, mask: _lib.Mask, layer_ptr, offset_ptr, label_ptr, n_rows: int,
