@@ -731,6 +731,84 @@ int pyas_spell_combine_grid(pyas_ctx *ctx, const pyas_spell *in, const pyas_grid
 int pyas_spell_finalize(pyas_ctx *ctx, const pyas_spell *in, int64_t n, int32_t stat,
                         int32_t *value, uint8_t *masked, void *stream);
 
+/* ---- where the extreme lies (Active.argmax / Active.argmin) -------------------
+ * Partial record of the arg-extreme of a set of selected positions along one
+ * dim (16 bytes): the winning unmasked element.
+ *   value   the winner itself in the data's class, as in pyas_partial (f for
+ *           floats, carried exactly as f64; i for signed, u for unsigned
+ *           integers), the stored element untouched: the sign of a zero and a
+ *           NaN are the element's own
+ *   index   its global index along the dim (origin[c] + the index in chunk c)
+ *   n       unmasked positions
+ * Element b beats element a when b is a NaN and a is not, or when neither is a
+ * NaN and b > a (PYAS_ARGEXT_MAX) / b < a (PYAS_ARGEXT_MIN) compared in the
+ * data's class (8-byte integers exactly; -0.0 == +0.0); among equals, and
+ * between two NaNs, the smaller index wins (and at one index, which is one
+ * element, the smaller bit pattern: the order is total).  Masked elements take
+ * no part.
+ * The all-zero record is neutral, and so is every record with n == 0 (its
+ * other fields are written as 0).  merged(a, b): the winner of the two by the
+ * rule above, n adds.  The rule is a total order on (value, index), so the
+ * merge is associative and commutative: the combines may take the records in
+ * any order and give the same record.  index and n are int32: the dim holds
+ * fewer than 2^31 indices. */
+typedef struct {
+    pyas_scalar value;
+    int32_t index;
+    int32_t n;
+} pyas_argext;
+
+enum { PYAS_ARGEXT_MAX = 0, PYAS_ARGEXT_MIN = 1 };
+typedef struct {
+    int32_t dim;             /* the chunk dim the index runs along: the one reduced dim */
+    int32_t which;           /* PYAS_ARGEXT_MAX / PYAS_ARGEXT_MIN */
+    const int32_t *origin;   /* device [n_chunks]: global index along dim of chunk c's local index 0
+                              * (the chunk coordinate times the chunk extent, as pyas_coord.origin) */
+} pyas_argext_rule;
+
+/* pyas_spell_axes for argext records: out[out_offsets[c] + o] receives the
+ * record of output o (C order over the kept selected dims) of chunk c, over the
+ * chunk's selected positions along rule->dim.  axes_mask must be
+ * 1u << rule->dim; which must be one of the two and origin non-NULL
+ * (PYAS_EINVAL otherwise, and when rule is NULL).  out_offsets may be NULL only
+ * for a 1-D variable (chunk c's record at out[c]).  When rule->dim is the
+ * innermost dim a wave owns an output: lane k takes positions k, k + 64, ...
+ * and the lanes' records are merged with shuffles (the merge is commutative);
+ * otherwise a lane walks its output's positions.  A per-element walk for any
+ * selection and mask: it has no speed target.  Other errors as
+ * pyas_moments_axes. */
+int pyas_argext_axes(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask,
+                     const pyas_argext_rule *rule, uint32_t axes_mask, const int64_t *out_offsets,
+                     pyas_argext *out, void *stream);
+/* The dense path of a box query: pyas_argext_axes + pyas_argext_combine_grid in
+ * ONE launch that writes one finished record per final output (out, device, C
+ * order over grid->out_extent) and no per-chunk records.  The caller's promises
+ * and the grid fields read are those of pyas_trend_cols.  rule->dim must be 0,
+ * the single reduced dim (grid->axes_mask == 1), with at least one kept dim
+ * behind it, and the mask must have no vector tables: otherwise PYAS_ENOTSUP,
+ * nothing is launched and the caller takes pyas_argext_axes.  A lane owns 4
+ * consecutive outputs along the innermost dim and walks them through every row
+ * of every chunk layer in increasing index order, keeping the best value, its
+ * row and the count in registers (updated by selects; a strict "beats" keeps
+ * the first occurrence), so a record is the lane's own (nothing is merged) and
+ * equals the two-step path's exactly. */
+int pyas_argext_cols(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask,
+                     const pyas_argext_rule *rule, const pyas_grid *grid, pyas_argext *out,
+                     void *stream);
+/* pyas_moments_combine_segments / pyas_moments_combine_grid for argext records
+ * (same orders, same errors).  The merge compares values in the data's class,
+ * so both take the data's dtype (pyas_dtype; PYAS_ENOTSUP when it is none of
+ * the ten) and which (PYAS_EINVAL when it is neither of the two). */
+int pyas_argext_combine_segments(pyas_ctx *ctx, int32_t dtype, int32_t which, const pyas_argext *in,
+                                 const int64_t *index, const int64_t *seg_offsets, int64_t n_segments,
+                                 pyas_argext *out, void *stream);
+int pyas_argext_combine_grid(pyas_ctx *ctx, int32_t dtype, int32_t which, const pyas_argext *in,
+                             const pyas_grid *grid, pyas_argext *out, void *stream);
+/* index[i] = the index of record i as int32, masked[i] = (n == 0), all device:
+ * 5 bytes per output cross PCIe instead of 16.  A masked index is 0. */
+int pyas_argext_finalize(pyas_ctx *ctx, const pyas_argext *in, int64_t n, int32_t *index,
+                         uint8_t *masked, void *stream);
+
 /* ---- per-label second moments (Active.grouped) -------------------------------
  * The pyas_moments record, one per (output, group): an element whose global
  * index along one reduced dim is i belongs to group labels[i] >= 0, or to no

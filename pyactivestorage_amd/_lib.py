@@ -84,6 +84,19 @@ SPELL_OPS = {"gt": 0, "ge": 1, "lt": 2, "le": 3}              # PYAS_SPELL_GT ..
 SPELL_STATS = {"longest": 0, "days": 1, "events": 2}          # PYAS_SPELL_LONGEST .. PYAS_SPELL_EVENTS
 
 
+class Argext(ctypes.Structure):
+    """pyas_argext: the winning element of an arg-extreme (its value, its global index) and the unmasked count."""
+    _fields_ = [("value", Scalar), ("index", ctypes.c_int32), ("n", ctypes.c_int32)]
+
+
+class ArgextRule(ctypes.Structure):
+    """pyas_argext_rule: the dim the index runs along, max or min, and each chunk's origin along it (device)."""
+    _fields_ = [("dim", ctypes.c_int32), ("which", ctypes.c_int32), ("origin", ctypes.c_void_p)]
+
+
+ARGEXT_WHICH = {"max": 0, "min": 1}                           # PYAS_ARGEXT_MAX, PYAS_ARGEXT_MIN
+
+
 class GroupRows(ctypes.Structure):
     """pyas_group_rows: the sorted reduced rows of a box query (device pointers) and the group count."""
     _fields_ = [("layer", ctypes.c_void_p), ("offset", ctypes.c_void_p), ("label", ctypes.c_void_p),
@@ -231,6 +244,8 @@ WSUM_NBYTES = ctypes.sizeof(Wsum)
 assert WSUM_NBYTES == 32
 SPELL_NBYTES = ctypes.sizeof(Spell)
 assert SPELL_NBYTES == 40
+ARGEXT_NBYTES = ctypes.sizeof(Argext)
+assert ARGEXT_NBYTES == 16
 
 _vp = ctypes.c_void_p
 _i32 = ctypes.c_int32
@@ -303,6 +318,13 @@ SIGNATURES = {
     "pyas_spell_combine_segments": [_vp, _vp, _vp, _vp, _i64, _vp, _vp],
     "pyas_spell_combine_grid": [_vp, _vp, ctypes.POINTER(Grid), _vp, _vp],
     "pyas_spell_finalize": [_vp, _vp, _i64, _i32, _vp, _vp, _vp],
+    "pyas_argext_axes": [_vp, ctypes.POINTER(Batch), ctypes.POINTER(Mask), ctypes.POINTER(ArgextRule), _u32, _vp, _vp,
+                         _vp],
+    "pyas_argext_cols": [_vp, ctypes.POINTER(Batch), ctypes.POINTER(Mask), ctypes.POINTER(ArgextRule),
+                         ctypes.POINTER(Grid), _vp, _vp],
+    "pyas_argext_combine_segments": [_vp, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp],
+    "pyas_argext_combine_grid": [_vp, _i32, _i32, _vp, ctypes.POINTER(Grid), _vp, _vp],
+    "pyas_argext_finalize": [_vp, _vp, _i64, _vp, _vp, _vp],
     "pyas_group_cols": [_vp, ctypes.POINTER(Batch), ctypes.POINTER(Mask), ctypes.POINTER(GroupRows),
                         ctypes.POINTER(Grid), _vp, _vp],
     "pyas_group_axes": [_vp, ctypes.POINTER(Batch), ctypes.POINTER(Mask), ctypes.POINTER(GroupLists), _u32, _vp, _vp,

@@ -52,8 +52,8 @@ import warnings
 
 import numpy as np
 
-from . import _lib, comoments, engine, grouped, histogram, moments, quantile, selection, spell, trend, weighted, \
-    zerosign
+from . import _lib, argext, comoments, engine, grouped, histogram, moments, quantile, selection, spell, trend, \
+    weighted, zerosign
 from .batch import ReductionPlan, _all_full
 from .device import DeviceBuffer, get_context
 from .dtypes import native, sum_dtype
@@ -358,6 +358,22 @@ def _sign_fallback(err):
     warnings.warn(f"the sign of a zero min/max is not NumPy's for this query ({err})",
                   RuntimeWarning, stacklevel=3)
 
+def _selection_position(index, bad, dim):
+    """Global indices along a dimension (``bad``: the masked entries, whose
+    index is 0 and whose position stays 0) as positions in its selection:
+    ``dim`` is the dimension's indexer, a slice of step >= 1 or a strictly
+    increasing index array."""
+    if dim.kind == "slice":
+        pos = index - dim.start if dim.start else index
+        if dim.step != 1:
+            pos = pos // dim.step
+        if not dim.start:
+            return pos                    # (the entries of ``bad`` are 0 already)
+    else:
+        pos = np.searchsorted(dim.sel, index).astype(np.int64)
+    return np.where(bad, 0, pos)
+
+
 class Active:
     """GPU-backed ``Active`` over one chunked variable."""
 
@@ -414,6 +430,8 @@ class Active:
         self._grouped_path = None       # the last grouped query: "cols" (dense column kernel) or "walk"
         self._spell = None              # spell: {"along", "op", "threshold", "stat", "min_length"} of the next query
         self._spell_path = None         # the last spell query: "cols" (dense column kernel) or "walk"
+        self._argext = None             # argmax / argmin: {"along", "which", "name"} of the next query
+        self._argext_path = None        # the last argmax / argmin query: "cols" (dense column kernel) or "walk"
         self._select_stats = None       # the last quantile query: its digit width, count launches and chains
         self._max_threads = int(max_threads)
         self.device = device
@@ -461,6 +479,15 @@ class Active:
         self._trend = None
         self._grouped = None
         self._spell = None
+        self._argext = None
+
+    @property
+    def argext_path(self):
+        """Which kernel the last :meth:`argmax` / :meth:`argmin` query ran:
+        ``"cols"`` (the dense column walk, pyas_argext_cols) or ``"walk"``
+        (the per-element walk, pyas_argext_axes); None before the first one
+        and after a query that reached no kernel (an empty selection)."""
+        return self._argext_path
 
     @property
     def spell_path(self):
@@ -669,6 +696,53 @@ class Active:
         self._axis = (d,)
         return self
 
+    def argmax(self, along):
+        """Where the maximum lies along one dimension, per output, in one pass
+        on the device: ``a.argmax(0)[index]`` is the position in the selection
+        along ``along`` of the largest unmasked element, what
+        ``np.argmax(data[index], axis=along)`` gives for unmasked data, as an
+        int64 masked array of the selection's shape with ``along`` kept at
+        extent 1, masked where an output has no unmasked element.  Masked
+        elements (``_FillValue``, ``missing_value``, ``valid_min``,
+        ``valid_max``) never win; among elements equal to the extreme the
+        first position wins; ``-0.0`` and ``+0.0`` are equal; if an unmasked
+        element is a NaN the first unmasked NaN wins, as in NumPy; values are
+        compared in the variable's own type (8-byte integers exactly).
+        ``along``: an int in ``[-ndim, ndim)``, the only reduced axis.  The
+        selection along ``along`` must be a slice of step >= 1, a strictly
+        increasing index list or a boolean mask (ValueError otherwise) of
+        fewer than 2^31 positions; any hyperslab on the other dims.  With
+        ``components`` a dict of ``position`` (the result), ``index`` (the
+        global index along ``along`` in the variable, int64), ``value`` (the
+        winning element itself, bit for bit, in the variable's dtype, masked
+        like the result) and ``n`` (the count of unmasked elements, int64,
+        never masked); ``argext.merge`` joins the components of selections
+        that lie along ``along`` (years, files).  ``value`` is the element at
+        ``index``: the sign of a zero is that element's, so it may differ from
+        :attr:`method` ``"max"`` / ``"min"``, which follow NumPy's tie rule
+        for zeros of both signs.  A unit-step box query with
+        ``along=0`` and a dimension behind it runs the dense column kernel
+        (pyas_argext_cols), anything else the per-element walk
+        (pyas_argext_axes): see :attr:`argext_path`; both give the same
+        records.  The setting holds for one query."""
+        return self._set_argext("argmax", along, "max")
+
+    def argmin(self, along):
+        """Where the minimum lies along one dimension: :meth:`argmax` with
+        the smallest unmasked element as the winner.  A NaN still wins over
+        every number (the first unmasked NaN), as in ``np.argmin``."""
+        return self._set_argext("argmin", along, "min")
+
+    def _set_argext(self, name, along, which):
+        try:
+            d = argext.check_along(along, self.ds.ndim)
+        except ValueError as exc:
+            raise ValueError(f"{name}: {exc}") from None
+        self._argext = {"along": d, "which": which, "name": name}
+        self._method = name
+        self._axis = (d,)
+        return self
+
     def grouped(self, stat, along, labels, axis=None, ddof=0, n_groups=None):
         """One statistic per label along a reduced dimension, in one pass on
         the device: ``stat`` (``"mean"``, ``"var"``, ``"std"``, ``"count"``,
@@ -815,6 +889,7 @@ class Active:
             self._trend = None           # and a trend's coordinate
             self._grouped = None         # and a grouped query's labels
             self._spell = None           # and a spell's threshold
+            self._argext = None          # and an arg-extreme's dimension
             for store in held:
                 _unhold(store)
             self._held.stores = []
@@ -847,6 +922,9 @@ class Active:
         sp = self._method == "spell"
         if sp and self.group is not None:
             raise NotImplementedError("spell with group=…: spell records are reduced on one GPU only")
+        ax = self._method in ("argmax", "argmin")
+        if ax and self.group is not None:
+            raise NotImplementedError(f"{self._method} with group=…: arg-extreme records are reduced on one GPU only")
         if self._axis is None:
             self._axis = tuple(range(ds.ndim))
         elif isinstance(self._axis, int):
@@ -858,10 +936,10 @@ class Active:
             raise ValueError(f"grouped: along={self._grouped['along']} is not among the reduced axes "
                              f"{self._norm_axes()}: every output would hold one label")
         cache_key = None
-        # (var / std, weighted, histogram, quantile, cov / corr, trend, grouped and spell queries bypass the plan
-        # cache: its plans replay pyas_partial launches)
+        # (var / std, weighted, histogram, quantile, cov / corr, trend, grouped, spell and arg-extreme queries bypass
+        # the plan cache: its plans replay pyas_partial launches)
         if self.resident and self.group is None and self._method is not None and not second and not has_w \
-                and not hist and not quant and not co and not tr and not gr and not sp:
+                and not hist and not quant and not co and not tr and not gr and not sp and not ax:
             ikey = _index_key(index)
             if ikey is not None:
                 cache_key = (ikey, self._norm_axes(), _missing_key(self.missing))
@@ -872,6 +950,10 @@ class Active:
             decode_filters(ds.filter_pipeline, ds.dtype.itemsize, ds.name)
         if sp:
             self._check_spell_index(index)
+        if ax:
+            self._check_ordered_index(index, self._argext["along"], self._method,
+                                      "positions follow the selection in increasing order",
+                                      "positions follow the selection in order")
         indexer = OrthogonalIndexer(index, ds.shape, ds.chunks)
         if self.components and self._method is None:       # active.py:483-485
             raise ValueError("Setting components to True for None statistical method.")
@@ -897,6 +979,8 @@ class Active:
             return self._reduce_grouped(indexer, compressor, filters, self._norm_axes())
         if sp:
             return self._reduce_spell(indexer, compressor, filters)
+        if ax:
+            return self._reduce_argext(indexer, compressor, filters)
         return self._reduce(indexer, compressor, filters, self._norm_axes(), cache_key)
 
     def _norm_axes(self):
@@ -1517,22 +1601,29 @@ class Active:
         slice of step >= 1, a strictly increasing index list or a boolean
         mask.  ValueError otherwise (what no statistic accepts is left to the
         planner's own errors)."""
-        d = self._spell["along"]
+        self._check_ordered_index(index, self._spell["along"], "spell",
+                                  "runs follow the selection in increasing order",
+                                  "runs follow the selection in order")
+
+    def _check_ordered_index(self, index, d, who, why_step, why_list):
+        """The order check of :meth:`_check_spell_index` for the statistic
+        ``who`` along dimension ``d`` (``why_*``: the reason its messages
+        give)."""
         s = _normalize(index, self.ds.ndim)[d]
         if isinstance(s, slice):
             if isinstance(s.step, (int, np.integer)) and s.step < 1:
-                raise ValueError(f"spell: the slice along dimension {d} has step {s.step}; runs follow the "
-                                 "selection in increasing order, so the step must be >= 1")
+                raise ValueError(f"{who}: the slice along dimension {d} has step {s.step}; {why_step}, so the step "
+                                 "must be >= 1")
             return
         if isinstance(s, (list, np.ndarray)) and np.ndim(s) > 0:
             a = np.asarray(s)
             if a.ndim == 1 and a.dtype.kind in "iu":
                 a = np.where(a < 0, a.astype(np.int64) + self.ds.shape[d], a.astype(np.int64))
                 if a.size > 1 and not bool(np.all(np.diff(a) > 0)):
-                    raise ValueError(f"spell: the index list along dimension {d} must be strictly increasing "
-                                     "(no repeats): runs follow the selection in order")
+                    raise ValueError(f"{who}: the index list along dimension {d} must be strictly increasing "
+                                     f"(no repeats): {why_list}")
             return
-        raise ValueError(f"spell: the index along dimension {d} must be a slice, an increasing index list or a "
+        raise ValueError(f"{who}: the index along dimension {d} must be a slice, an increasing index list or a "
                          f"boolean mask. Got {s!r}")
 
     def _reduce_spell(self, indexer, compressor, filters):
@@ -1599,6 +1690,84 @@ class Active:
             out["events_total"] = spell.finalize(parts, "events")
             return out
         return spell.finalize(parts, self._spell["stat"])
+
+    # -- argmax / argmin ---------------------------------------------------------
+    def _reduce_argext(self, indexer, compressor, filters):
+        """argmax / argmin: records of the winning element along the one
+        reduced axis.  A unit-step box query with ``along == 0`` and a dim
+        behind it takes the dense column kernel (pyas_argext_cols: one
+        finished record per output, the chunk layers walked in the kernel);
+        anything else per-chunk records (pyas_argext_axes) merged in the
+        orders of :meth:`_reduce_records`.  The index and its mask come back
+        from the device (pyas_argext_finalize) unless ``components`` is set;
+        the host turns the global index into the position in the selection."""
+        ds = self.ds
+        ae = self._argext
+        along, which, axes = ae["along"], ae["which"], (ae["along"],)
+        self._argext_path = None
+        dim = indexer.dim_indexers[along]
+        if dim.nitems >= 2 ** 31 or dim.nchunks * ds.chunks[along] >= 2 ** 31:
+            raise NotImplementedError(f"{ae['name']}: {dim.nitems} selected positions of {ds.shape[along]} along "
+                                      f"dimension {along}; the record holds the index in int32 (fewer than 2^31)")
+        q = self._query_plan(indexer, compressor, filters, axes)
+        final_shape, n_final = q.final_shape, q.n_final
+        if q.empty:
+            return self._format_argext(np.zeros(final_shape, dtype=engine.argext_dtype), dim)
+        ctx, st, plan = q.ctx, q.st, q.plan
+        # origin[c]: the global index of chunk c's local index 0 along the axis
+        coords = np.asarray(q.coords, dtype=np.int64).reshape(-1, ds.ndim)
+        origin = (coords[:, along] * ds.chunks[along]).astype(np.int32)
+        obuf = DeviceBuffer(ctx, origin.nbytes)
+        ctx.h2d(obuf.ptr, origin, st)
+        fin = DeviceBuffer(ctx, n_final * _lib.ARGEXT_NBYTES)
+
+        def launch(off_ptr, out_ptr):
+            engine.argext_axes(ctx, plan.batch, plan.mask_up.struct, along, which, obuf.ptr, off_ptr, out_ptr, st)
+
+        def combine_segments(ctx, *args):
+            engine.argext_combine_segments(ctx, ds.dtype, which, *args)
+
+        def combine_grid(ctx, *args):
+            engine.argext_combine_grid(ctx, ds.dtype, which, *args)
+        # the dense path: every dim one unit-step range, axis 0 reduced, a kept dim behind it
+        dense = q.dims is not None and axes == (0,) and ds.ndim > 1 and bool(np.all(q.table[:, :ds.ndim, 1] == 1))
+        done = False
+        if dense:
+            g = _grid_struct(ds.ndim, axes, final_shape, {"n_coords": [len(p) for p in q.dims]}, None, None)
+            done = engine.argext_cols(ctx, plan.batch, plan.mask_up.struct, along, which, obuf.ptr, g, fin.ptr, st)
+        keep = []
+        if not done:
+            fin, keep = self._reduce_records(q, axes, _lib.ARGEXT_NBYTES, launch, combine_segments, combine_grid,
+                                             fin=fin)
+        self._argext_path = "cols" if done else "walk"
+        if self._components:
+            final = self._records_back(q, fin, keep, engine.argext_dtype)
+            del keep, obuf
+            return self._format_argext(final, dim)
+        # the index and its mask on the device: 5 bytes per output come back
+        vbuf = DeviceBuffer(ctx, n_final * 5)
+        engine.argext_finalize(ctx, fin.ptr, n_final, vbuf.ptr, vbuf.ptr + 4 * n_final, st)
+        val = np.empty(n_final, dtype=np.int32)
+        msk = np.empty(n_final, dtype=np.uint8)
+        ctx.d2h(val, vbuf.ptr, st)
+        ctx.d2h(msk, vbuf.ptr + 4 * n_final, st)
+        ctx.synchronize(st)
+        del keep, obuf
+        bad = msk.reshape(final_shape).astype(bool)
+        return np.ma.MaskedArray(_selection_position(val.reshape(final_shape).astype(np.int64), bad, dim), mask=bad)
+
+    def _format_argext(self, parts, dim):
+        """The int64 result of an argmax / argmin query from its combined
+        records on the host (``dim``: the indexer of the axis), or its
+        components."""
+        index = argext.finalize(parts)
+        bad = np.ma.getmaskarray(index)
+        pos = np.ma.MaskedArray(_selection_position(index.data.copy(), bad, dim), mask=bad)
+        if self._components:
+            return {"position": pos, "index": index,
+                    "value": np.ma.MaskedArray(argext.values(parts, self.ds.dtype), mask=bad),
+                    "n": np.ma.MaskedArray(parts["n"].astype(np.int64), mask=np.zeros(parts.shape, dtype=bool))}
+        return pos
 
     # -- grouped -----------------------------------------------------------------
     def _reduce_grouped(self, indexer, compressor, filters, axes):

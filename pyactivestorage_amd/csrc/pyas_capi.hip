@@ -1921,6 +1921,141 @@ int pyas_spell_finalize(pyas_ctx *ctx, const pyas_spell *in, int64_t n, int32_t 
     return PYAS_OK;
 }
 
+// pyas_argext_axes / pyas_argext_cols: the checks of the rule
+static int check_argext(const pyas_argext_rule *rule, int ndim, uint32_t axes_mask) {
+    if (!rule) return fail(PYAS_EINVAL, "rule is NULL");
+    if (rule->dim < 0 || rule->dim >= ndim) return fail(PYAS_EINVAL, "argext dim %d outside rank %d", rule->dim, ndim);
+    if (axes_mask != (1u << rule->dim))
+        return fail(PYAS_EINVAL, "axes mask 0x%x is not the argext dim %d alone", axes_mask, rule->dim);
+    if (rule->which != PYAS_ARGEXT_MAX && rule->which != PYAS_ARGEXT_MIN)
+        return fail(PYAS_EINVAL, "which = %d", rule->which);
+    if (!rule->origin) return fail(PYAS_EINVAL, "origin is NULL");
+    return PYAS_OK;
+}
+
+int pyas_argext_axes(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask, const pyas_argext_rule *rule,
+                     uint32_t axes_mask, const int64_t *out_offsets, pyas_argext *out, void *stream) {
+    if (!ctx) return fail(PYAS_EINVAL, "ctx is NULL");
+    if (batch && (batch->ndim < 1 || batch->ndim > PYAS_MAX_DIMS))
+        return fail(PYAS_ENOTSUP, "chunk rank %d outside 1..%d", batch->ndim, PYAS_MAX_DIMS);
+    pyas::ArgextArgs x;
+    std::memset(&x, 0, sizeof(x));
+    int es;
+    bool shuf, bsw, masked;
+    int rc = prepare(ctx, batch, mask, x.r, es, shuf, bsw, masked);
+    if (rc) return rc;
+    rc = check_argext(rule, batch->ndim, axes_mask);
+    if (rc) return rc;
+    const int64_t n = batch->n_chunks;
+    if (n == 0) return PYAS_OK;
+    if (!out) return fail(PYAS_EINVAL, "out is NULL");
+    if (batch->ndim > 1 && !out_offsets) return fail(PYAS_EINVAL, "out_offsets is NULL");
+    PYAS_HIP(hipSetDevice(ctx->device));
+    x.dim = rule->dim;
+    x.out_offsets = out_offsets;
+    x.out = out;
+    x.origin = rule->origin;
+    x.neg = rule->which == PYAS_ARGEXT_MIN;
+    x.shuf = shuf;
+    x.bswap = bsw;
+    axes_geometry(batch->ndim, batch->chunk_shape, axes_mask, x.row, x.bpc);   // (1-D: one wave per chunk)
+    const int64_t grid = n * x.bpc;
+    if (grid >= (int64_t(1) << 31)) return fail(PYAS_ENOTSUP, "grid too large");
+    PYAS_HIP(pyas::launch_argext_axes(batch->dtype, x, grid, (hipStream_t)stream));
+    return PYAS_OK;
+}
+
+int pyas_argext_cols(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask, const pyas_argext_rule *rule,
+                     const pyas_grid *g, pyas_argext *out, void *stream) {
+    if (!ctx) return fail(PYAS_EINVAL, "ctx is NULL");
+    if (!g) return fail(PYAS_EINVAL, "grid is NULL");
+    if (batch && (batch->ndim < 1 || batch->ndim > PYAS_MAX_DIMS))
+        return fail(PYAS_ENOTSUP, "chunk rank %d outside 1..%d", batch->ndim, PYAS_MAX_DIMS);
+    pyas::ArgextColsArgs x;
+    std::memset(&x, 0, sizeof(x));
+    int es;
+    bool shuf, bsw, masked;
+    int rc = prepare(ctx, batch, mask, x.r, es, shuf, bsw, masked);
+    if (rc) return rc;
+    const int nd = batch->ndim;
+    if (g->ndim != nd) return fail(PYAS_EINVAL, "grid rank %d, chunk rank %d", g->ndim, nd);
+    rc = check_argext(rule, nd, g->axes_mask);
+    if (rc) return rc;
+    int64_t n_layers = 1, n_cols = 1;
+    for (int d = 0; d < nd; ++d) {
+        if (g->n_coords[d] < 1) return fail(PYAS_EINVAL, "n_coords[%d] = %lld", d, (long long)g->n_coords[d]);
+        if ((g->axes_mask >> d) & 1u) {
+            n_layers *= g->n_coords[d];
+        } else {
+            if (g->out_extent[d] < 1) return fail(PYAS_EINVAL, "out_extent[%d] = %lld", d, (long long)g->out_extent[d]);
+            n_cols *= g->n_coords[d];
+        }
+    }
+    if (batch->n_chunks != n_layers * n_cols)
+        return fail(PYAS_EINVAL, "%lld chunks for a grid of %lld", (long long)batch->n_chunks,
+                    (long long)(n_layers * n_cols));
+    // the geometry the column walk takes: dim 0 reduced, at least one kept dim behind it
+    if (rule->dim != 0 || nd < 2) return fail(PYAS_ENOTSUP, "argext dim %d of rank %d is not dim 0 before a kept dim", rule->dim, nd);
+    if (x.r.tab.on[0] || x.r.tab.on[1]) return fail(PYAS_ENOTSUP, "vector mask tables");
+    if (!out) return fail(PYAS_EINVAL, "out is NULL");
+    int64_t items = (batch->chunk_shape[nd - 1] + pyas::kTrendV - 1) / pyas::kTrendV;
+    for (int d = 1; d < nd - 1; ++d) items *= batch->chunk_shape[d];
+    const int64_t bpc = (items + pyas::kBlock - 1) / pyas::kBlock;
+    const int64_t grid = n_cols * bpc;
+    if (grid >= (int64_t(1) << 31)) return fail(PYAS_ENOTSUP, "grid of %lld workgroups", (long long)grid);
+    PYAS_HIP(hipSetDevice(ctx->device));
+    int64_t stride = 1;
+    for (int d = nd - 1; d >= 0; --d) {
+        x.n_coords[d] = g->n_coords[d];
+        x.ostride[d] = stride;
+        if (d >= 1) stride *= g->out_extent[d];
+    }
+    x.n_layers = n_layers;
+    x.n_cols = n_cols;
+    x.bpc = bpc;
+    x.out = out;
+    x.origin = rule->origin;
+    x.neg = rule->which == PYAS_ARGEXT_MIN;
+    x.bswap = bsw;
+    x.masked = masked;
+    PYAS_HIP(pyas::launch_argext_cols(batch->dtype, x, shuf, grid, (hipStream_t)stream));
+    return PYAS_OK;
+}
+
+// the combines of argext records: the merge of the dtype's class and the direction
+static int check_argext_merge(int32_t dtype, int32_t which) {
+    if (dtype < PYAS_I8 || dtype > PYAS_F64) return fail(PYAS_ENOTSUP, "dtype = %d", dtype);
+    if (which != PYAS_ARGEXT_MAX && which != PYAS_ARGEXT_MIN) return fail(PYAS_EINVAL, "which = %d", which);
+    return PYAS_OK;
+}
+
+int pyas_argext_combine_segments(pyas_ctx *ctx, int32_t dtype, int32_t which, const pyas_argext *in,
+                                 const int64_t *index, const int64_t *seg_offsets, int64_t n_segments,
+                                 pyas_argext *out, void *stream) {
+    const int rc = check_argext_merge(dtype, which);
+    if (rc) return rc;
+    return combine_segments_records(ctx, in, index, seg_offsets, n_segments, out, stream,
+                                    pyas::launch_argext_segments(dtype, which == PYAS_ARGEXT_MIN));
+}
+
+int pyas_argext_combine_grid(pyas_ctx *ctx, int32_t dtype, int32_t which, const pyas_argext *in, const pyas_grid *g,
+                             pyas_argext *out, void *stream) {
+    const int rc = check_argext_merge(dtype, which);
+    if (rc) return rc;
+    return combine_grid_records(ctx, in, g, out, stream, pyas::launch_argext_grid(dtype, which == PYAS_ARGEXT_MIN));
+}
+
+int pyas_argext_finalize(pyas_ctx *ctx, const pyas_argext *in, int64_t n, int32_t *index, uint8_t *masked,
+                         void *stream) {
+    if (!ctx) return fail(PYAS_EINVAL, "ctx is NULL");
+    if (n < 0) return fail(PYAS_EINVAL, "negative record count");
+    if (n == 0) return PYAS_OK;
+    if (!in || !index || !masked) return fail(PYAS_EINVAL, "NULL argument");
+    PYAS_HIP(hipSetDevice(ctx->device));
+    PYAS_HIP(pyas::launch_argext_finalize(in, n, index, masked, (hipStream_t)stream));
+    return PYAS_OK;
+}
+
 // pyas_group_cols / pyas_group_cols_partial: the checks and the geometry, then
 // `launch` (launch_group_cols or launch_group_cols_partial) over `out`
 typedef hipError_t (*group_cols_launch)(int, const pyas::GroupColsArgs &, bool, int64_t, hipStream_t);

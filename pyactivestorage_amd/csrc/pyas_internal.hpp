@@ -395,6 +395,40 @@ hipError_t launch_spell_grid(const pyas_spell *in, const pyas_grid &g, int64_t n
                              pyas_spell *out, hipStream_t st);
 hipError_t launch_spell_finalize(const pyas_spell *in, int64_t n, int32_t stat, int32_t *value, uint8_t *masked,
                                  hipStream_t st);
+// arg-extremes (pyas_argext.hip): pyas_argext records, merged in any order
+struct ArgextArgs {
+    ReduceArgs r;                     // r.out unused
+    int32_t dim;                      // the one reduced dim
+    int64_t bpc;                      // workgroups per chunk
+    const int64_t *out_offsets;       // NULL (1-D variables only): chunk c's record at out[c]
+    pyas_argext *out;
+    const int32_t *origin;            // [n_chunks]: the global index along dim of chunk c's local index 0
+    bool neg;                         // argmin
+    bool shuf, bswap;
+    bool row;                         // dim is the innermost dim: a wave per output
+};
+struct ArgextColsArgs {
+    ReduceArgs r;                     // r.out unused; r.sel NULL: whole chunks
+    int64_t n_coords[PYAS_MAX_DIMS];  // chunk coordinates per dim (chunk n = C-order position)
+    int64_t ostride[PYAS_MAX_DIMS];   // final-output element strides (kept dims)
+    int64_t n_layers, n_cols;         // chunks along dim 0 / the kept dims
+    int64_t bpc;                      // workgroups per column
+    pyas_argext *out;                 // one finished record per final output
+    const int32_t *origin;            // [n_chunks]: the global row of chunk c's row 0
+    bool neg;                         // argmin
+    bool bswap, masked;
+};
+hipError_t launch_argext_axes(int dtype, const ArgextArgs &a, int64_t grid, hipStream_t st);
+hipError_t launch_argext_cols(int dtype, const ArgextColsArgs &a, bool shuf, int64_t grid, hipStream_t st);
+// the combines' launchers for the class of `dtype` and the direction (the merge compares in that class)
+typedef hipError_t (*argext_segments_fn)(const pyas_argext *, const int64_t *, const int64_t *, int64_t,
+                                         pyas_argext *, hipStream_t);
+typedef hipError_t (*argext_grid_fn)(const pyas_argext *, const pyas_grid &, int64_t, int64_t, pyas_argext *,
+                                     hipStream_t);
+argext_segments_fn launch_argext_segments(int dtype, bool neg);
+argext_grid_fn launch_argext_grid(int dtype, bool neg);
+hipError_t launch_argext_finalize(const pyas_argext *in, int64_t n, int32_t *index, uint8_t *masked,
+                                  hipStream_t st);
 // per-label second moments (pyas_grouped.hip): pyas_moments records, one per (output, group)
 constexpr int kGroupV = 4;            // k_group_cols: consecutive outputs per lane
 constexpr int kGroupRows = PYAS_GROUP_ROWS;   // k_group_cols: rows of the sorted list staged in LDS per pass (16 KiB)

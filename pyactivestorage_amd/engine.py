@@ -35,6 +35,10 @@ comoments_dtype = np.dtype([("count", "<i8"), ("mean_x", "<f8"), ("mean_y", "<f8
 spell_dtype = np.dtype([(name, "<i4") for name in ("n", "n_true", "len", "head", "tail", "best", "days", "events",
                                                    "min_length", "reserved")])
 
+# Host view of ``pyas_argext``; ``value`` holds the bits of the pyas_scalar (view it as f8 / i8 / u8 by the
+# data's class: :func:`pyactivestorage_amd.argext.values`)
+argext_dtype = np.dtype([("value", "<u8"), ("index", "<i4"), ("n", "<i4")])
+
 # Host view of ``pyas_wsum``
 wsum_dtype = np.dtype([("count", "<i8"), ("sw", "<f8"), ("swx", "<f8"), ("reserved", "<u8")])
 
@@ -341,6 +345,56 @@ def spell_finalize(ctx: Context, in_ptr, n: int, stat: str, value_ptr, mask_ptr,
     ``n`` records as int32 values and mask bytes, on the device."""
     _lib.check(ctx.lib.pyas_spell_finalize(ctx.handle, in_ptr, int(n), _lib.SPELL_STATS[stat], value_ptr, mask_ptr,
                                            stream), "pyas_spell_finalize")
+
+
+def _argext_rule(dim: int, which: str, origin_ptr) -> _lib.ArgextRule:
+    return _lib.ArgextRule(int(dim), _lib.ARGEXT_WHICH[which], origin_ptr)
+
+
+def argext_axes(ctx: Context, batch: _lib.Batch, mask: _lib.Mask, dim: int, which: str, origin_ptr,
+                out_offsets_ptr, out_ptr, stream) -> None:
+    """pyas_argext_axes: arg-extreme records (``which``: ``max`` or ``min``)
+    along chunk dim ``dim`` (the one reduced dim) per chunk output, laid out
+    like :func:`moments_axes`'; ``origin_ptr``: each chunk's global index 0
+    along ``dim`` (device int32)."""
+    rule = _argext_rule(dim, which, origin_ptr)
+    _lib.check(ctx.lib.pyas_argext_axes(ctx.handle, ctypes.byref(batch), ctypes.byref(mask), ctypes.byref(rule),
+                                        1 << int(dim), out_offsets_ptr, out_ptr, stream), "pyas_argext_axes")
+
+
+def argext_cols(ctx: Context, batch: _lib.Batch, mask: _lib.Mask, dim: int, which: str, origin_ptr,
+                grid: _lib.Grid, out_ptr, stream) -> bool:
+    """pyas_argext_cols: one finished record per final output of a unit-step
+    box query, in one launch.  False (nothing launched) when the geometry is
+    not the dense path's (PYAS_ENOTSUP): the caller runs :func:`argext_axes`."""
+    rule = _argext_rule(dim, which, origin_ptr)
+    rc = ctx.lib.pyas_argext_cols(ctx.handle, ctypes.byref(batch), ctypes.byref(mask), ctypes.byref(rule),
+                                  ctypes.byref(grid), out_ptr, stream)
+    if rc == _lib.ENOTSUP:
+        return False
+    _lib.check(rc, "pyas_argext_cols")
+    return True
+
+
+def argext_combine_segments(ctx: Context, dt, which: str, in_ptr, index_ptr, seg_ptr, n_seg, out_ptr,
+                            stream) -> None:
+    """pyas_argext_combine_segments (``index_ptr`` None: the identity) for
+    records of data of dtype ``dt``."""
+    _lib.check(ctx.lib.pyas_argext_combine_segments(ctx.handle, dtype_code(dt), _lib.ARGEXT_WHICH[which], in_ptr,
+                                                    index_ptr, seg_ptr, int(n_seg), out_ptr, stream),
+               "pyas_argext_combine_segments")
+
+
+def argext_combine_grid(ctx: Context, dt, which: str, in_ptr, grid: _lib.Grid, out_ptr, stream) -> None:
+    _lib.check(ctx.lib.pyas_argext_combine_grid(ctx.handle, dtype_code(dt), _lib.ARGEXT_WHICH[which], in_ptr,
+                                                ctypes.byref(grid), out_ptr, stream), "pyas_argext_combine_grid")
+
+
+def argext_finalize(ctx: Context, in_ptr, n: int, index_ptr, mask_ptr, stream) -> None:
+    """pyas_argext_finalize: the global index of ``n`` records as int32 and
+    the mask bytes, on the device."""
+    _lib.check(ctx.lib.pyas_argext_finalize(ctx.handle, in_ptr, int(n), index_ptr, mask_ptr, stream),
+               "pyas_argext_finalize")
 
 
 def group_cols(ctx: Context, batch: _lib.Batch, mask: _lib.Mask, layer_ptr, offset_ptr, label_ptr, n_rows: int,
