@@ -809,6 +809,97 @@ int pyas_argext_combine_grid(pyas_ctx *ctx, int32_t dtype, int32_t which, const 
 int pyas_argext_finalize(pyas_ctx *ctx, const pyas_argext *in, int64_t n, int32_t *index,
                          uint8_t *masked, void *stream);
 
+/* ---- conditional reductions past a threshold (Active.exceed) ------------------
+ * Partial record of the selected positions of an output (32 bytes).  A position
+ * is true when its element is unmasked and float64(x) op t holds, t the
+ * output's threshold (values convert as astype(float64) does; a NaN element
+ * compares false but counts as unmasked; a masked element is false; a NaN
+ * threshold, which is how the host hands over a masked field entry, makes
+ * nothing true).
+ *   n        unmasked positions
+ *   n_true   true positions
+ *   sum      sum of float64(x) over the true positions, in f64 from the first
+ *            addition
+ *   excess   sum over the true positions of one f64 subtraction each: x - t for
+ *            GT / GE, t - x for LT / LE (never derived from sum - t n_true)
+ * The all-zero record is neutral; merged(a, b) adds field by field.  The
+ * integer fields are exact on every path; sum and excess depend on the order of
+ * the additions in the last bits, and every kernel and combine of the library
+ * adds in a fixed order, so a result is bit-identical from run to run. */
+typedef struct {
+    int64_t n;
+    int64_t n_true;
+    double sum;
+    double excess;
+} pyas_exceed;
+
+/* A threshold per output: the field as the caller gave it, in C order over its
+ * own shape (the variable's extent on every kept dim, 1 on every reduced dim).
+ * The threshold of an output of chunk c whose kept dims' indices inside the
+ * chunk are local[d] is values[origin[c] + sum_d local[d] * stride[d]]. */
+typedef struct {
+    const double *values;    /* device: the field; NaN where an entry is masked */
+    const int64_t *origin;   /* device [n_chunks]: the field offset of chunk c's local index 0 */
+    int64_t stride[PYAS_MAX_DIMS];   /* field element stride per dim; 0 on reduced dims */
+} pyas_exceed_field;
+
+enum { PYAS_EXCEED_COUNT = 0, PYAS_EXCEED_FRACTION = 1, PYAS_EXCEED_SUM = 2, PYAS_EXCEED_MEAN = 3,
+       PYAS_EXCEED_EXCESS = 4 };
+typedef struct {
+    int32_t op;              /* PYAS_SPELL_GT / GE / LT / LE */
+    int32_t reserved;
+    double threshold;        /* finite; read when field is NULL */
+    const pyas_exceed_field *field;   /* NULL: one threshold for every output */
+} pyas_exceed_rule;
+
+/* pyas_moments_axes for exceed records: out[out_offsets[c] + o] receives the
+ * record of output o (C order over the kept selected dims) of chunk c over the
+ * chunk's selected positions along the dims of axes_mask, any subset of the
+ * dims.  op must be one of the four; a scalar threshold must be finite; a field
+ * needs both tables and is refused when every dim is reduced (a field of one
+ * entry is a scalar): PYAS_EINVAL otherwise, and when rule is NULL.  With every
+ * dim reduced a workgroup takes a tile of a chunk (a contiguous selection
+ * streams 16-B loads) and the tiles are merged in tile order; out_offsets may
+ * then be NULL (chunk c's record at out[c]).  Otherwise a lane owns an output
+ * when the innermost dim is kept and a wave owns it when that dim is reduced
+ * (lanes merged with shuffles in a fixed order); the output's threshold is
+ * loaded once per output.  Other errors as pyas_moments_axes. */
+int pyas_exceed_axes(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask,
+                     const pyas_exceed_rule *rule, uint32_t axes_mask, const int64_t *out_offsets,
+                     pyas_exceed *out, void *stream);
+/* The dense path of a box query: pyas_exceed_axes + pyas_exceed_combine_grid in
+ * ONE launch that writes one finished record per final output (out, device, C
+ * order over grid->out_extent) and no per-chunk records.  The caller's promises,
+ * the grid fields read and the geometries served are those of pyas_trend_cols:
+ * the reduced dims are a leading prefix 0 .. P-1 of the dims with at least one
+ * kept dim behind them, the mask has no vector tables, and an output covers
+ * fewer than 2^32 chunk positions: otherwise PYAS_ENOTSUP, nothing is launched
+ * and the caller takes pyas_exceed_axes.  A lane owns 4 consecutive outputs
+ * along the innermost dim, loads their 4 thresholds once (from the field by
+ * the formula above) and walks them through every row of every chunk layer in
+ * increasing index order, so a record is the lane's own (nothing is merged).
+ * n and n_true equal the two-step path's; sum and excess may differ from it in
+ * the last bits (another summation order). */
+int pyas_exceed_cols(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask,
+                     const pyas_exceed_rule *rule, const pyas_grid *grid, pyas_exceed *out,
+                     void *stream);
+/* pyas_moments_combine_segments / pyas_moments_combine_grid for exceed records
+ * (same orders, same errors). */
+int pyas_exceed_combine_segments(pyas_ctx *ctx, const pyas_exceed *in, const int64_t *index,
+                                 const int64_t *seg_offsets, int64_t n_segments,
+                                 pyas_exceed *out, void *stream);
+int pyas_exceed_combine_grid(pyas_ctx *ctx, const pyas_exceed *in, const pyas_grid *grid,
+                             pyas_exceed *out, void *stream);
+/* One statistic (stat: PYAS_EXCEED_*) of n records, all device: 8 bytes at
+ * value + 8 i (an int64 for COUNT, a double for the rest) and the byte
+ * masked[i], so 9 bytes per output cross PCIe instead of 32.
+ *   COUNT n_true, FRACTION n_true / n, SUM sum, EXCESS excess: masked when n == 0
+ *   MEAN sum / n_true: masked when n_true == 0
+ * and masked as well where thr_masked[i] != 0 (device, one byte per output:
+ * the output's threshold is masked; NULL: none is).  A masked value is 0. */
+int pyas_exceed_finalize(pyas_ctx *ctx, const pyas_exceed *in, int64_t n, int32_t stat,
+                         const uint8_t *thr_masked, void *value, uint8_t *masked, void *stream);
+
 /* ---- per-label second moments (Active.grouped) -------------------------------
  * The pyas_moments record, one per (output, group): an element whose global
  * index along one reduced dim is i belongs to group labels[i] >= 0, or to no

@@ -97,6 +97,27 @@ class ArgextRule(ctypes.Structure):
 ARGEXT_WHICH = {"max": 0, "min": 1}                           # PYAS_ARGEXT_MAX, PYAS_ARGEXT_MIN
 
 
+class Exceed(ctypes.Structure):
+    """pyas_exceed: the unmasked and the true positions of an output, and the sums of x and |x - t| over the true."""
+    _fields_ = [("n", ctypes.c_int64), ("n_true", ctypes.c_int64), ("sum", ctypes.c_double),
+                ("excess", ctypes.c_double)]
+
+
+class ExceedField(ctypes.Structure):
+    """pyas_exceed_field: the per-output thresholds, each chunk's origin in them (device pointers) and the strides."""
+    _fields_ = [("values", ctypes.c_void_p), ("origin", ctypes.c_void_p), ("stride", ctypes.c_int64 * MAX_DIMS)]
+
+
+class ExceedRule(ctypes.Structure):
+    """pyas_exceed_rule: the comparison, the scalar threshold and the field (NULL: the scalar)."""
+    _fields_ = [("op", ctypes.c_int32), ("reserved", ctypes.c_int32), ("threshold", ctypes.c_double),
+                ("field", ctypes.POINTER(ExceedField))]
+
+
+# PYAS_EXCEED_COUNT .. PYAS_EXCEED_EXCESS
+EXCEED_STATS = {"count": 0, "fraction": 1, "sum": 2, "mean": 3, "excess": 4}
+
+
 class GroupRows(ctypes.Structure):
     """pyas_group_rows: the sorted reduced rows of a box query (device pointers) and the group count."""
     _fields_ = [("layer", ctypes.c_void_p), ("offset", ctypes.c_void_p), ("label", ctypes.c_void_p),
@@ -246,6 +267,8 @@ SPELL_NBYTES = ctypes.sizeof(Spell)
 assert SPELL_NBYTES == 40
 ARGEXT_NBYTES = ctypes.sizeof(Argext)
 assert ARGEXT_NBYTES == 16
+EXCEED_NBYTES = ctypes.sizeof(Exceed)
+assert EXCEED_NBYTES == 32
 
 _vp = ctypes.c_void_p
 _i32 = ctypes.c_int32
@@ -325,6 +348,13 @@ SIGNATURES = {
     "pyas_argext_combine_segments": [_vp, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp],
     "pyas_argext_combine_grid": [_vp, _i32, _i32, _vp, ctypes.POINTER(Grid), _vp, _vp],
     "pyas_argext_finalize": [_vp, _vp, _i64, _vp, _vp, _vp],
+    "pyas_exceed_axes": [_vp, ctypes.POINTER(Batch), ctypes.POINTER(Mask), ctypes.POINTER(ExceedRule), _u32, _vp, _vp,
+                         _vp],
+    "pyas_exceed_cols": [_vp, ctypes.POINTER(Batch), ctypes.POINTER(Mask), ctypes.POINTER(ExceedRule),
+                         ctypes.POINTER(Grid), _vp, _vp],
+    "pyas_exceed_combine_segments": [_vp, _vp, _vp, _vp, _i64, _vp, _vp],
+    "pyas_exceed_combine_grid": [_vp, _vp, ctypes.POINTER(Grid), _vp, _vp],
+    "pyas_exceed_finalize": [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp],
     "pyas_group_cols": [_vp, ctypes.POINTER(Batch), ctypes.POINTER(Mask), ctypes.POINTER(GroupRows),
                         ctypes.POINTER(Grid), _vp, _vp],
     "pyas_group_axes": [_vp, ctypes.POINTER(Batch), ctypes.POINTER(Mask), ctypes.POINTER(GroupLists), _u32, _vp, _vp,

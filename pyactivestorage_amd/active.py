@@ -52,7 +52,7 @@ import warnings
 
 import numpy as np
 
-from . import _lib, argext, comoments, engine, grouped, histogram, moments, quantile, selection, spell, trend, \
+from . import _lib, argext, comoments, engine, exceed, grouped, histogram, moments, quantile, selection, spell, trend, \
     weighted, zerosign
 from .batch import ReductionPlan, _all_full
 from .device import DeviceBuffer, get_context
@@ -432,6 +432,8 @@ class Active:
         self._spell_path = None         # the last spell query: "cols" (dense column kernel) or "walk"
         self._argext = None             # argmax / argmin: {"along", "which", "name"} of the next query
         self._argext_path = None        # the last argmax / argmin query: "cols" (dense column kernel) or "walk"
+        self._exceed = None             # exceed: {"op", "threshold", "stat"} of the next query
+        self._exceed_path = None        # the last exceed query: "cols" (dense column kernel) or "walk"
         self._select_stats = None       # the last quantile query: its digit width, count launches and chains
         self._max_threads = int(max_threads)
         self.device = device
@@ -480,6 +482,16 @@ class Active:
         self._grouped = None
         self._spell = None
         self._argext = None
+        self._exceed = None
+
+    @property
+    def exceed_path(self):
+        """Which kernel the last :meth:`exceed` query ran: ``"cols"`` (the dense
+        column walk, pyas_exceed_cols) or ``"walk"`` (pyas_exceed_axes: the
+        per-element walk, or the tile kernel when every dim is reduced); None
+        before the first one and after a query that reached no kernel (an
+        empty selection)."""
+        return self._exceed_path
 
     @property
     def argext_path(self):
@@ -743,6 +755,67 @@ class Active:
         self._axis = (d,)
         return self
 
+    def exceed(self, op, threshold, stat="count", axis=None):
+        """Counts, sums and degree days past a threshold, per output, in one
+        pass on the device (frost and summer days, R10mm, PRCPTOT, SDII,
+        R95pTOT, TX90p, heating and cooling degree days).  An element is
+        *true* when it is selected, unmasked and ``float64(x) op threshold``
+        holds (``op``: ``"gt"``, ``"ge"``, ``"lt"`` or ``"le"``; a NaN compares
+        false but counts as unmasked; a masked element is never true).  Every
+        element converts as ``astype(float64)`` does, so 8-byte integers
+        compare as their float64 conversion: ``2**53 + 1`` is not ``gt``
+        ``2**53``.  ``axis``: any subset of the dims, as for :meth:`var`.
+        ``threshold`` is a finite real scalar, or a per-output field:
+        array-like with ``ndim`` dims whose extent is ``shape[d]`` on every
+        kept dim and 1 on every reduced one, converted to float64 and indexed
+        by *global* index (like ``weights``, ``coord`` and ``labels``), so
+        slices, steps, index lists and boolean masks on the kept dims pick the
+        matching thresholds; a full-variable ``a.quantile(q, axis=axes)[...]``
+        is a valid field for ``axis=axes`` as it stands.  A field must be
+        finite everywhere except at the masked entries of a masked array:
+        nothing compares true there and the result is masked there.  A field
+        with every dim reduced has one entry and is the scalar case.
+        ValueError for a wrong rank or shape.  ``stat``: ``"count"``, the
+        number of true elements (int64); ``"fraction"``, ``n_true / n``;
+        ``"sum"``, the sum of the true elements in float64 from the first
+        addition (0.0 when nothing is true); ``"mean"``, ``sum / n_true``;
+        ``"excess"``, the sum over the true elements of ``|x - threshold|``,
+        each term one float64 subtraction (``x - t`` for ``gt`` / ``ge``,
+        ``t - x`` for ``lt`` / ``le``) added in float64, never derived from
+        ``sum - t n_true``.  The query returns a masked array of
+        ``final_shape`` (reduced dims kept at extent 1), float64 except
+        ``count``, masked where the output has no unmasked element (``mean``:
+        no true element) and where its threshold is masked.  With
+        ``components`` a dict of ``n``, ``n_true`` (int64), ``sum`` and
+        ``excess`` (float64), none of them masked (``n_true == 0`` where the
+        threshold is masked); ``exceed.merge`` adds the components of
+        disjoint selections (years, files) and assumes the same ``op`` and
+        the same threshold on both sides, and ``exceed.finalize`` reads a
+        result from them.  A unit-step box query whose reduced axes are a
+        leading prefix of the dims (``axis=(0,)``) runs the dense column
+        kernel (pyas_exceed_cols), anything else pyas_exceed_axes: see
+        :attr:`exceed_path`; both give the same ``n`` and ``n_true``, and
+        sums that may differ in the last bits.  The settings hold for one
+        query."""
+        before = self._axis
+        try:
+            op, stat = spell.check_op(op), exceed.check_stat(stat)
+            if axis is not None:
+                self._axis = axis
+            if self._axis is None:
+                axes = tuple(range(self.ds.ndim))
+            else:
+                if isinstance(self._axis, int):
+                    self._axis = (self._axis,)
+                axes = self._norm_axes()
+            field = exceed.check_field(threshold, self.ds.shape, axes)
+        except ValueError as exc:
+            self._axis = before
+            raise ValueError(f"exceed: {exc}") from None
+        self._exceed = {"op": op, "stat": stat, "field": field, "axes": axes}
+        self._method = "exceed"
+        return self
+
     def grouped(self, stat, along, labels, axis=None, ddof=0, n_groups=None):
         """One statistic per label along a reduced dimension, in one pass on
         the device: ``stat`` (``"mean"``, ``"var"``, ``"std"``, ``"count"``,
@@ -890,6 +963,7 @@ class Active:
             self._grouped = None         # and a grouped query's labels
             self._spell = None           # and a spell's threshold
             self._argext = None          # and an arg-extreme's dimension
+            self._exceed = None          # and an exceed query's threshold
             for store in held:
                 _unhold(store)
             self._held.stores = []
@@ -925,6 +999,9 @@ class Active:
         ax = self._method in ("argmax", "argmin")
         if ax and self.group is not None:
             raise NotImplementedError(f"{self._method} with group=…: arg-extreme records are reduced on one GPU only")
+        ex = self._method == "exceed"
+        if ex and self.group is not None:
+            raise NotImplementedError("exceed with group=…: exceed records are reduced on one GPU only")
         if self._axis is None:
             self._axis = tuple(range(ds.ndim))
         elif isinstance(self._axis, int):
@@ -936,10 +1013,10 @@ class Active:
             raise ValueError(f"grouped: along={self._grouped['along']} is not among the reduced axes "
                              f"{self._norm_axes()}: every output would hold one label")
         cache_key = None
-        # (var / std, weighted, histogram, quantile, cov / corr, trend, grouped, spell and arg-extreme queries bypass
-        # the plan cache: its plans replay pyas_partial launches)
+        # (var / std, weighted, histogram, quantile, cov / corr, trend, grouped, spell, arg-extreme and exceed queries
+        # bypass the plan cache: its plans replay pyas_partial launches)
         if self.resident and self.group is None and self._method is not None and not second and not has_w \
-                and not hist and not quant and not co and not tr and not gr and not sp and not ax:
+                and not hist and not quant and not co and not tr and not gr and not sp and not ax and not ex:
             ikey = _index_key(index)
             if ikey is not None:
                 cache_key = (ikey, self._norm_axes(), _missing_key(self.missing))
@@ -981,6 +1058,8 @@ class Active:
             return self._reduce_spell(indexer, compressor, filters)
         if ax:
             return self._reduce_argext(indexer, compressor, filters)
+        if ex:
+            return self._reduce_exceed(indexer, compressor, filters, self._norm_axes())
         return self._reduce(indexer, compressor, filters, self._norm_axes(), cache_key)
 
     def _norm_axes(self):
@@ -1768,6 +1847,121 @@ class Active:
                     "value": np.ma.MaskedArray(argext.values(parts, self.ds.dtype), mask=bad),
                     "n": np.ma.MaskedArray(parts["n"].astype(np.int64), mask=np.zeros(parts.shape, dtype=bool))}
         return pos
+
+    # -- exceed ------------------------------------------------------------------
+    def _exceed_field_tables(self, q, axes):
+        """pyas_exceed_field of this query for the chunks at ``q.coords``: the
+        field's element strides (0 on reduced dims) and each chunk's origin in
+        it (two NumPy expressions: nothing loops per chunk or per output)."""
+        ds = self.ds
+        stride = np.zeros(ds.ndim, dtype=np.int64)
+        step = 1
+        for d in range(ds.ndim - 1, -1, -1):
+            if d not in axes:
+                stride[d] = step
+                step *= ds.shape[d]
+        coords = np.asarray(q.coords, dtype=np.int64).reshape(-1, ds.ndim)
+        origin = (coords * np.asarray(ds.chunks, dtype=np.int64)) @ stride
+        return stride, np.ascontiguousarray(origin, dtype=np.int64)
+
+    @staticmethod
+    def _exceed_thr_masked(indexer, field, axes):
+        """The field's mask at the selection, in the final outputs' order
+        (uint8, flat), or None when no entry is masked."""
+        if field.mask is None:
+            return None
+        picks = []
+        for d, dim in enumerate(indexer.dim_indexers):
+            if d in axes:
+                picks.append(np.zeros(1, dtype=np.int64))
+            elif dim.kind == "slice":
+                picks.append(np.arange(dim.start, dim.stop, dim.step, dtype=np.int64))
+            else:
+                picks.append(dim.sel)
+        return np.ascontiguousarray(field.mask[np.ix_(*picks)], dtype=np.uint8).reshape(-1)
+
+    def _reduce_exceed(self, indexer, compressor, filters, axes):
+        """exceed: records of the counts and sums past the threshold.  A
+        unit-step box query whose reduced axes are a leading prefix of the dims
+        takes the dense column kernel (pyas_exceed_cols: one finished record
+        per output, the chunk layers walked in the kernel); anything else
+        per-chunk records (pyas_exceed_axes) merged in the orders of
+        :meth:`_reduce_records`.  A threshold field is uploaded as it is, with
+        one origin per chunk (the kernels index it by global index).  The
+        statistic and its mask are computed on the device
+        (pyas_exceed_finalize) unless ``components`` is set."""
+        ds = self.ds
+        ex = self._exceed
+        field, stat = ex["field"], ex["stat"]
+        self._exceed_path = None
+        if axes != ex["axes"]:
+            raise ValueError(f"exceed: the reduced axes changed from {ex['axes']} to {axes} after the threshold was "
+                             "checked against them")
+        q = self._query_plan(indexer, compressor, filters, axes)
+        final_shape, n_final = q.final_shape, q.n_final
+        thr_masked = np.ones(n_final, dtype=np.uint8) if field.all_masked else \
+            self._exceed_thr_masked(indexer, field, axes)
+        if q.empty:
+            return self._format_exceed(np.zeros(final_shape, dtype=engine.exceed_dtype), thr_masked)
+        ctx, st, plan = q.ctx, q.st, q.plan
+        fin = DeviceBuffer(ctx, n_final * _lib.EXCEED_NBYTES)
+        fbuf = None
+        if field.values is not None:
+            stride, origin = self._exceed_field_tables(q, axes)
+            fbuf = DeviceBuffer(ctx, field.values.nbytes + origin.nbytes)
+            ctx.h2d(fbuf.ptr, field.values, st)
+            ctx.h2d(fbuf.ptr + field.values.nbytes, origin, st)
+            rule = engine.exceed_rule(ex["op"], 0.0, (fbuf.ptr, fbuf.ptr + field.values.nbytes, stride))
+        else:
+            rule = engine.exceed_rule(ex["op"], field.scalar)
+
+        def launch(off_ptr, out_ptr):
+            engine.exceed_axes(ctx, plan.batch, plan.mask_up.struct, rule, q.axes_mask, off_ptr, out_ptr, st)
+        # the dense path: every dim one unit-step range, reduced axes 0 .. P-1, a kept dim behind them
+        dense = q.dims is not None and len(axes) < ds.ndim and axes == tuple(range(len(axes))) \
+            and bool(np.all(q.table[:, :ds.ndim, 1] == 1))
+        done = False
+        if dense:
+            g = _grid_struct(ds.ndim, axes, final_shape, {"n_coords": [len(p) for p in q.dims]}, None, None)
+            done = engine.exceed_cols(ctx, plan.batch, plan.mask_up.struct, rule, g, fin.ptr, st)
+        keep = []
+        if not done:
+            fin, keep = self._reduce_records(q, axes, _lib.EXCEED_NBYTES, launch, engine.exceed_combine_segments,
+                                             engine.exceed_combine_grid, fin=fin)
+        self._exceed_path = "cols" if done else "walk"
+        if self._components:
+            final = self._records_back(q, fin, keep, engine.exceed_dtype)
+            del keep, fbuf
+            return self._format_exceed(final, thr_masked)
+        # the statistic and its mask on the device: 9 bytes per output come back
+        tm_bytes = n_final if thr_masked is not None else 0
+        vbuf = DeviceBuffer(ctx, n_final * 9 + tm_bytes)
+        tm_ptr = None
+        if thr_masked is not None:
+            tm_ptr = vbuf.ptr + 9 * n_final
+            ctx.h2d(tm_ptr, thr_masked, st)
+        engine.exceed_finalize(ctx, fin.ptr, n_final, stat, tm_ptr, vbuf.ptr, vbuf.ptr + 8 * n_final, st)
+        val = np.empty(n_final, dtype=np.int64 if stat == "count" else np.float64)
+        msk = np.empty(n_final, dtype=np.uint8)
+        ctx.d2h(val, vbuf.ptr, st)
+        ctx.d2h(msk, vbuf.ptr + 8 * n_final, st)
+        ctx.synchronize(st)
+        del keep, fbuf
+        return np.ma.MaskedArray(val.reshape(final_shape), mask=msk.reshape(final_shape).astype(bool))
+
+    def _format_exceed(self, parts, thr_masked):
+        """The result of an exceed query from its combined records on the host
+        (exceed.finalize), or its components; ``thr_masked``: the flat bytes of
+        :meth:`_exceed_thr_masked` or None."""
+        tm = None if thr_masked is None else thr_masked.reshape(parts.shape).astype(bool)
+        if self._components:
+            if tm is not None and tm.any():   # (a one-entry masked field ran as a scalar)
+                parts = parts.copy()
+                for name in ("n_true", "sum", "excess"):
+                    parts[name][tm] = 0
+            return {name: np.ma.MaskedArray(np.ascontiguousarray(parts[name]), mask=np.zeros(parts.shape, dtype=bool))
+                    for name in exceed.FIELDS}
+        return exceed.finalize(parts, self._exceed["stat"], tm)
 
     # -- grouped -----------------------------------------------------------------
     def _reduce_grouped(self, indexer, compressor, filters, axes):

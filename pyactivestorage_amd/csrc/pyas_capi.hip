@@ -2056,6 +2056,159 @@ int pyas_argext_finalize(pyas_ctx *ctx, const pyas_argext *in, int64_t n, int32_
     return PYAS_OK;
 }
 
+// pyas_exceed_axes / pyas_exceed_cols: the checks of the rule, and the rule as the kernels test it
+static int check_exceed(const pyas_exceed_rule *rule, int ndim, uint32_t axes_mask, pyas::ExcTest &t) {
+    if (!rule) return fail(PYAS_EINVAL, "rule is NULL");
+    if (rule->op < PYAS_SPELL_GT || rule->op > PYAS_SPELL_LE) return fail(PYAS_EINVAL, "op = %d", rule->op);
+    t.neg = rule->op == PYAS_SPELL_LT || rule->op == PYAS_SPELL_LE;   // x < t as -x > -t
+    t.incl = rule->op == PYAS_SPELL_GE || rule->op == PYAS_SPELL_LE;
+    const pyas_exceed_field *f = rule->field;
+    if (!f) {
+        if (!std::isfinite(rule->threshold)) return fail(PYAS_EINVAL, "threshold is not finite");
+        t.threshold = t.neg ? -rule->threshold : rule->threshold;
+        return PYAS_OK;
+    }
+    if (!f->values || !f->origin) return fail(PYAS_EINVAL, "threshold field has a NULL table");
+    if (axes_mask == (1u << ndim) - 1u)
+        return fail(PYAS_EINVAL, "a threshold field with every dim reduced: pass its one entry as the scalar");
+    for (int d = 0; d < ndim; ++d) {
+        if (f->stride[d] < 0) return fail(PYAS_EINVAL, "field stride[%d] = %lld", d, (long long)f->stride[d]);
+        if (((axes_mask >> d) & 1u) && f->stride[d] != 0)
+            return fail(PYAS_EINVAL, "field stride[%d] = %lld on a reduced dim", d, (long long)f->stride[d]);
+        t.stride[d] = f->stride[d];
+    }
+    t.values = f->values;
+    t.origin = f->origin;
+    return PYAS_OK;
+}
+
+int pyas_exceed_axes(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask, const pyas_exceed_rule *rule,
+                     uint32_t axes_mask, const int64_t *out_offsets, pyas_exceed *out, void *stream) {
+    if (!ctx) return fail(PYAS_EINVAL, "ctx is NULL");
+    if (batch && (batch->ndim < 1 || batch->ndim > PYAS_MAX_DIMS))
+        return fail(PYAS_ENOTSUP, "chunk rank %d outside 1..%d", batch->ndim, PYAS_MAX_DIMS);
+    pyas::ExceedArgs x;
+    std::memset(&x, 0, sizeof(x));
+    int es;
+    bool shuf, bsw, masked;
+    int rc = prepare(ctx, batch, mask, x.r, es, shuf, bsw, masked);
+    if (rc) return rc;
+    if (axes_mask >> batch->ndim) return fail(PYAS_EINVAL, "axes mask 0x%x beyond rank %d", axes_mask, batch->ndim);
+    rc = check_exceed(rule, batch->ndim, axes_mask, x.t);
+    if (rc) return rc;
+    const int64_t n = batch->n_chunks;
+    if (n == 0) return PYAS_OK;
+    if (!out) return fail(PYAS_EINVAL, "out is NULL");
+    PYAS_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    x.axes = axes_mask;
+    x.out_offsets = out_offsets;
+    x.out = out;
+    x.bswap = bsw;
+    x.masked = masked;
+    if (axes_mask == (1u << batch->ndim) - 1u) {
+        // every dim reduced: a workgroup per (chunk, tile); tiles merge in tile order
+        int64_t grid;
+        rc = full_geometry(ctx, stream, n, x.r.chunk_elems * es, x.bpc, grid, x.tiles);
+        if (rc) return rc;
+        PYAS_HIP(pyas::launch_exceed_full(batch->dtype, x, shuf, grid, st));
+        if (x.bpc > 1) PYAS_HIP(pyas::launch_exceed_tiles(x.tiles, x.bpc, n, out_offsets, out, st));
+        return PYAS_OK;
+    }
+    if (!out_offsets) return fail(PYAS_EINVAL, "out_offsets is NULL");
+    axes_geometry(batch->ndim, batch->chunk_shape, axes_mask, x.row, x.bpc);
+    const int64_t grid = n * x.bpc;
+    if (grid >= (int64_t(1) << 31)) return fail(PYAS_ENOTSUP, "grid too large");
+    PYAS_HIP(pyas::launch_exceed_axes(batch->dtype, x, shuf, grid, st));
+    return PYAS_OK;
+}
+
+int pyas_exceed_cols(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask, const pyas_exceed_rule *rule,
+                     const pyas_grid *g, pyas_exceed *out, void *stream) {
+    if (!ctx) return fail(PYAS_EINVAL, "ctx is NULL");
+    if (!g) return fail(PYAS_EINVAL, "grid is NULL");
+    if (batch && (batch->ndim < 1 || batch->ndim > PYAS_MAX_DIMS))
+        return fail(PYAS_ENOTSUP, "chunk rank %d outside 1..%d", batch->ndim, PYAS_MAX_DIMS);
+    pyas::ExceedColsArgs x;
+    std::memset(&x, 0, sizeof(x));
+    int es;
+    bool shuf, bsw, masked;
+    int rc = prepare(ctx, batch, mask, x.r, es, shuf, bsw, masked);
+    if (rc) return rc;
+    const int nd = batch->ndim;
+    if (g->ndim != nd) return fail(PYAS_EINVAL, "grid rank %d, chunk rank %d", g->ndim, nd);
+    if (g->axes_mask >> nd) return fail(PYAS_EINVAL, "axes mask 0x%x beyond rank %d", g->axes_mask, nd);
+    rc = check_exceed(rule, nd, g->axes_mask, x.t);
+    if (rc) return rc;
+    int64_t n_layers = 1, n_cols = 1;
+    for (int d = 0; d < nd; ++d) {
+        if (g->n_coords[d] < 1) return fail(PYAS_EINVAL, "n_coords[%d] = %lld", d, (long long)g->n_coords[d]);
+        if ((g->axes_mask >> d) & 1u) {
+            n_layers *= g->n_coords[d];
+        } else {
+            if (g->out_extent[d] < 1) return fail(PYAS_EINVAL, "out_extent[%d] = %lld", d, (long long)g->out_extent[d]);
+            n_cols *= g->n_coords[d];
+        }
+    }
+    if (batch->n_chunks != n_layers * n_cols)
+        return fail(PYAS_EINVAL, "%lld chunks for a grid of %lld", (long long)batch->n_chunks,
+                    (long long)(n_layers * n_cols));
+    // the geometries the column walk takes: reduced dims 0 .. P-1, at least one kept dim behind them
+    int P = 0;
+    while (P < nd && ((g->axes_mask >> P) & 1u)) ++P;
+    if (P == 0 || P == nd || g->axes_mask != (1u << P) - 1u)
+        return fail(PYAS_ENOTSUP, "reduced dims 0x%x are not a leading prefix with a kept dim behind it", g->axes_mask);
+    if (x.r.tab.on[0] || x.r.tab.on[1]) return fail(PYAS_ENOTSUP, "vector mask tables");
+    // a lane counts its outputs' positions in 32 bits
+    double positions = (double)n_layers;
+    for (int d = 0; d < P; ++d) positions *= (double)batch->chunk_shape[d];
+    if (positions >= 4294967296.0) return fail(PYAS_ENOTSUP, "2^32 or more positions per output");
+    if (!out) return fail(PYAS_EINVAL, "out is NULL");
+    int64_t items = (batch->chunk_shape[nd - 1] + pyas::kTrendV - 1) / pyas::kTrendV;
+    for (int d = P; d < nd - 1; ++d) items *= batch->chunk_shape[d];
+    const int64_t bpc = (items + pyas::kBlock - 1) / pyas::kBlock;
+    const int64_t grid = n_cols * bpc;
+    if (grid >= (int64_t(1) << 31)) return fail(PYAS_ENOTSUP, "grid of %lld workgroups", (long long)grid);
+    PYAS_HIP(hipSetDevice(ctx->device));
+    x.P = P;
+    int64_t stride = 1;
+    for (int d = nd - 1; d >= 0; --d) {
+        x.n_coords[d] = g->n_coords[d];
+        x.ostride[d] = stride;
+        if (d >= P) stride *= g->out_extent[d];
+    }
+    x.n_layers = n_layers;
+    x.n_cols = n_cols;
+    x.bpc = bpc;
+    x.out = out;
+    x.bswap = bsw;
+    x.masked = masked;
+    PYAS_HIP(pyas::launch_exceed_cols(batch->dtype, x, shuf, grid, (hipStream_t)stream));
+    return PYAS_OK;
+}
+
+int pyas_exceed_combine_segments(pyas_ctx *ctx, const pyas_exceed *in, const int64_t *index, const int64_t *seg_offsets,
+                                 int64_t n_segments, pyas_exceed *out, void *stream) {
+    return combine_segments_records(ctx, in, index, seg_offsets, n_segments, out, stream,
+                                    pyas::launch_exceed_segments);
+}
+
+int pyas_exceed_combine_grid(pyas_ctx *ctx, const pyas_exceed *in, const pyas_grid *g, pyas_exceed *out, void *stream) {
+    return combine_grid_records(ctx, in, g, out, stream, pyas::launch_exceed_grid);
+}
+
+int pyas_exceed_finalize(pyas_ctx *ctx, const pyas_exceed *in, int64_t n, int32_t stat, const uint8_t *thr_masked,
+                         void *value, uint8_t *masked, void *stream) {
+    if (!ctx) return fail(PYAS_EINVAL, "ctx is NULL");
+    if (n < 0) return fail(PYAS_EINVAL, "negative record count");
+    if (stat < PYAS_EXCEED_COUNT || stat > PYAS_EXCEED_EXCESS) return fail(PYAS_EINVAL, "stat = %d", stat);
+    if (n == 0) return PYAS_OK;
+    if (!in || !value || !masked) return fail(PYAS_EINVAL, "NULL argument");
+    PYAS_HIP(hipSetDevice(ctx->device));
+    PYAS_HIP(pyas::launch_exceed_finalize(in, n, stat, thr_masked, value, masked, (hipStream_t)stream));
+    return PYAS_OK;
+}
+
 // pyas_group_cols / pyas_group_cols_partial: the checks and the geometry, then
 // `launch` (launch_group_cols or launch_group_cols_partial) over `out`
 typedef hipError_t (*group_cols_launch)(int, const pyas::GroupColsArgs &, bool, int64_t, hipStream_t);

@@ -429,6 +429,47 @@ argext_segments_fn launch_argext_segments(int dtype, bool neg);
 argext_grid_fn launch_argext_grid(int dtype, bool neg);
 hipError_t launch_argext_finalize(const pyas_argext *in, int64_t n, int32_t *index, uint8_t *masked,
                                   hipStream_t st);
+// conditional reductions past a threshold (pyas_exceed.hip): pyas_exceed records, merged by addition
+struct ExcTest {
+    double threshold;                 // the scalar as the kernel compares: negated for lt / le
+    bool neg, incl;                   // lt / le: compare -x > -threshold; ge / le: equality counts
+    const double *values;             // pyas_exceed_field (NULL: the scalar)
+    const int64_t *origin;
+    int64_t stride[PYAS_MAX_DIMS];
+};
+struct ExceedArgs {
+    ReduceArgs r;                     // r.out unused
+    uint32_t axes;                    // reduced dims
+    int64_t bpc;                      // workgroups per chunk (full: tiles per chunk)
+    const int64_t *out_offsets;       // NULL (full only): chunk c's record at out[c]
+    pyas_exceed *out;
+    pyas_exceed *tiles;               // full with bpc > 1: one record per workgroup
+    ExcTest t;
+    bool bswap, masked;
+    bool row;                         // innermost dim reduced: a wave per output
+};
+struct ExceedColsArgs {
+    ReduceArgs r;                     // r.out unused; r.sel NULL: whole chunks
+    int32_t P;                        // dims 0 .. P-1 are reduced, P .. ndim-1 kept
+    int64_t n_coords[PYAS_MAX_DIMS];  // chunk coordinates per dim (chunk n = C-order position)
+    int64_t ostride[PYAS_MAX_DIMS];   // final-output element strides (kept dims)
+    int64_t n_layers, n_cols;         // chunks along the reduced dims / kept dims
+    int64_t bpc;                      // workgroups per column
+    pyas_exceed *out;                 // one finished record per final output
+    ExcTest t;
+    bool bswap, masked;
+};
+hipError_t launch_exceed_full(int dtype, const ExceedArgs &a, bool shuf, int64_t grid, hipStream_t st);
+hipError_t launch_exceed_axes(int dtype, const ExceedArgs &a, bool shuf, int64_t grid, hipStream_t st);
+hipError_t launch_exceed_cols(int dtype, const ExceedColsArgs &a, bool shuf, int64_t grid, hipStream_t st);
+hipError_t launch_exceed_tiles(const pyas_exceed *tiles, int64_t tpc, int64_t n_chunks, const int64_t *out_offsets,
+                               pyas_exceed *out, hipStream_t st);
+hipError_t launch_exceed_segments(const pyas_exceed *in, const int64_t *index, const int64_t *seg, int64_t n_seg,
+                                  pyas_exceed *out, hipStream_t st);
+hipError_t launch_exceed_grid(const pyas_exceed *in, const pyas_grid &g, int64_t n_out, int64_t n_layers,
+                              pyas_exceed *out, hipStream_t st);
+hipError_t launch_exceed_finalize(const pyas_exceed *in, int64_t n, int32_t stat, const uint8_t *thr_masked,
+                                  void *value, uint8_t *masked, hipStream_t st);
 // per-label second moments (pyas_grouped.hip): pyas_moments records, one per (output, group)
 constexpr int kGroupV = 4;            // k_group_cols: consecutive outputs per lane
 constexpr int kGroupRows = PYAS_GROUP_ROWS;   // k_group_cols: rows of the sorted list staged in LDS per pass (16 KiB)

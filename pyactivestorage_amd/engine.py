@@ -39,6 +39,9 @@ spell_dtype = np.dtype([(name, "<i4") for name in ("n", "n_true", "len", "head",
 # data's class: :func:`pyactivestorage_amd.argext.values`)
 argext_dtype = np.dtype([("value", "<u8"), ("index", "<i4"), ("n", "<i4")])
 
+# Host view of ``pyas_exceed``
+exceed_dtype = np.dtype([("n", "<i8"), ("n_true", "<i8"), ("sum", "<f8"), ("excess", "<f8")])
+
 # Host view of ``pyas_wsum``
 wsum_dtype = np.dtype([("count", "<i8"), ("sw", "<f8"), ("swx", "<f8"), ("reserved", "<u8")])
 
@@ -395,6 +398,62 @@ def argext_finalize(ctx: Context, in_ptr, n: int, index_ptr, mask_ptr, stream) -
     the mask bytes, on the device."""
     _lib.check(ctx.lib.pyas_argext_finalize(ctx.handle, in_ptr, int(n), index_ptr, mask_ptr, stream),
                "pyas_argext_finalize")
+
+
+def exceed_rule(op: str, threshold: float, field=None) -> _lib.ExceedRule:
+    """pyas_exceed_rule for a scalar ``threshold``, or for a per-output field
+    ``(values_ptr, origin_ptr, strides)`` (device pointers; one element stride
+    per dim, 0 on reduced dims).  The returned struct keeps the field struct
+    alive (``rule.field_struct``)."""
+    if field is None:
+        return _lib.ExceedRule(_lib.SPELL_OPS[op], 0, float(threshold), None)
+    values_ptr, origin_ptr, strides = field
+    f = _lib.ExceedField(values_ptr, origin_ptr, (ctypes.c_int64 * _lib.MAX_DIMS)(*[int(s) for s in strides]))
+    rule = _lib.ExceedRule(_lib.SPELL_OPS[op], 0, 0.0, ctypes.pointer(f))
+    rule.field_struct = f
+    return rule
+
+
+def exceed_axes(ctx: Context, batch: _lib.Batch, mask: _lib.Mask, rule: _lib.ExceedRule, axes_mask: int,
+                out_offsets_ptr, out_ptr, stream) -> None:
+    """pyas_exceed_axes: exceed records over the dims of ``axes_mask`` per
+    chunk output, laid out like :func:`moments_axes`' (``out_offsets_ptr`` may
+    be None only when every dim is reduced)."""
+    _lib.check(ctx.lib.pyas_exceed_axes(ctx.handle, ctypes.byref(batch), ctypes.byref(mask), ctypes.byref(rule),
+                                        int(axes_mask), out_offsets_ptr, out_ptr, stream), "pyas_exceed_axes")
+
+
+def exceed_cols(ctx: Context, batch: _lib.Batch, mask: _lib.Mask, rule: _lib.ExceedRule, grid: _lib.Grid, out_ptr,
+                stream) -> bool:
+    """pyas_exceed_cols: one finished record per final output of a unit-step
+    box query, in one launch.  False (nothing launched) when the geometry is
+    not the dense path's (PYAS_ENOTSUP): the caller runs :func:`exceed_axes`."""
+    rc = ctx.lib.pyas_exceed_cols(ctx.handle, ctypes.byref(batch), ctypes.byref(mask), ctypes.byref(rule),
+                                  ctypes.byref(grid), out_ptr, stream)
+    if rc == _lib.ENOTSUP:
+        return False
+    _lib.check(rc, "pyas_exceed_cols")
+    return True
+
+
+def exceed_combine_segments(ctx: Context, in_ptr, index_ptr, seg_ptr, n_seg, out_ptr, stream) -> None:
+    """pyas_exceed_combine_segments (``index_ptr`` None: the identity)."""
+    _lib.check(ctx.lib.pyas_exceed_combine_segments(ctx.handle, in_ptr, index_ptr, seg_ptr, int(n_seg), out_ptr,
+                                                    stream), "pyas_exceed_combine_segments")
+
+
+def exceed_combine_grid(ctx: Context, in_ptr, grid: _lib.Grid, out_ptr, stream) -> None:
+    _lib.check(ctx.lib.pyas_exceed_combine_grid(ctx.handle, in_ptr, ctypes.byref(grid), out_ptr, stream),
+               "pyas_exceed_combine_grid")
+
+
+def exceed_finalize(ctx: Context, in_ptr, n: int, stat: str, thr_masked_ptr, value_ptr, mask_ptr, stream) -> None:
+    """pyas_exceed_finalize: ``stat`` of ``n`` records (8 bytes each: int64
+    for ``count``, float64 otherwise) and the mask bytes, on the device;
+    ``thr_masked_ptr``: one byte per output, non-zero where its threshold is
+    masked, or None."""
+    _lib.check(ctx.lib.pyas_exceed_finalize(ctx.handle, in_ptr, int(n), _lib.EXCEED_STATS[stat], thr_masked_ptr,
+                                            value_ptr, mask_ptr, stream), "pyas_exceed_finalize")
 
 
 def group_cols(ctx: Context, batch: _lib.Batch, mask: _lib.Mask, layer_ptr, offset_ptr, label_ptr, n_rows: int,
