@@ -900,6 +900,91 @@ int pyas_exceed_combine_grid(pyas_ctx *ctx, const pyas_exceed *in, const pyas_gr
 int pyas_exceed_finalize(pyas_ctx *ctx, const pyas_exceed *in, int64_t n, int32_t stat,
                          const uint8_t *thr_masked, void *value, uint8_t *masked, void *stream);
 
+/* ---- running-window extremes (Active.rolling) ---------------------------------
+ * Partial record of the extreme window sum of a sequence of selected positions
+ * along one dim (144 bytes).  A window is w positions consecutive in the
+ * selection; it is valid when all w elements are unmasked (a NaN is data, not
+ * a masked element).  A valid window's sum is
+ *   s = f64(x[p]); s += f64(x[p+1]); ...; s += f64(x[p+w-1])
+ * (each element converts as astype(float64) does; w - 1 float64 additions,
+ * oldest element first: this order is the definition, nothing is added and
+ * subtracted along the way).  The extreme keeps the first among equal sums
+ * (-0.0 == +0.0) and the first NaN sum wins, as in np.max / np.min.
+ *   best         the extreme valid-window sum (0 when n_windows == 0)
+ *   position     of that window's first element within the piece (0 when none)
+ *   n_windows    valid windows
+ *   n, len       unmasked positions / positions
+ *   window       w (1 .. PYAS_ROLL_MAX_WINDOW), which: PYAS_ROLL_MAX / MIN; both
+ *                travel in the record so that a merge needs no argument
+ *   head[j]      the piece's element j, j < min(len, w - 1)
+ *   tail[k]      the piece's element len - 1 - k, k < min(len, w - 1): the LAST
+ *                element is tail[0]
+ *   head_ok, tail_ok   bit j: head[j] / tail[j] exists and is unmasked
+ * Slots that do not exist or are masked hold 0 and a clear bit, so equal
+ * pieces give equal bytes.  The all-zero record is neutral on either side.
+ * Merge (a before b, NOT commutative, associative), w = max of the windows:
+ *   every window of m = w-1 .. 1 elements of a's end and w - m of b's start
+ *   (valid when tail_ok bits 0 .. m-1 and head_ok bits 0 .. w-m-1 are set) is
+ *   summed by the rule above, at position a.len - m; the candidates a.best,
+ *   those windows by decreasing m, b.best (position + a.len) are taken in
+ *   this order, a later one winning only when it strictly beats a non-NaN
+ *   holder or is the first NaN; the counts add; head = the first
+ *   min(len, w-1) of a.head ++ b.head, tail likewise from the end.
+ * All counts are int32: a sequence holds fewer than 2^31 positions. */
+#define PYAS_ROLL_MAX_WINDOW 8
+typedef struct {
+    double best;
+    int32_t position, n_windows, n, len;
+    uint8_t window, which, head_ok, tail_ok;
+    int32_t reserved;
+    double head[PYAS_ROLL_MAX_WINDOW - 1], tail[PYAS_ROLL_MAX_WINDOW - 1];
+} pyas_roll;
+
+enum { PYAS_ROLL_MAX = 0, PYAS_ROLL_MIN = 1 };
+enum { PYAS_ROLL_SUM = 0, PYAS_ROLL_MEAN = 1 };
+typedef struct {
+    int32_t dim;             /* the chunk dim the windows follow: the one reduced dim */
+    int32_t window;          /* 1 .. PYAS_ROLL_MAX_WINDOW */
+    int32_t which;           /* PYAS_ROLL_MAX / PYAS_ROLL_MIN */
+} pyas_roll_rule;
+
+/* pyas_spell_axes for roll records: out[out_offsets[c] + o] receives the record
+ * of output o (C order over the kept selected dims) of chunk c, over the
+ * chunk's selected positions along rule->dim in selection order.  axes_mask
+ * must be 1u << rule->dim, window in 1 .. PYAS_ROLL_MAX_WINDOW and which one of
+ * the two (PYAS_EINVAL otherwise, and when rule is NULL).  out_offsets may be
+ * NULL only for a 1-D variable (chunk c's record at out[c]).  A lane walks its
+ * output's positions in order, whichever dim the windows follow: a
+ * per-element walk for any selection and mask, with no speed target.  Other
+ * errors as pyas_moments_axes. */
+int pyas_roll_axes(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask,
+                   const pyas_roll_rule *rule, uint32_t axes_mask, const int64_t *out_offsets,
+                   pyas_roll *out, void *stream);
+/* The dense path of a box query, as pyas_spell_cols (same promises, same grid
+ * fields, same PYAS_ENOTSUP cases with nothing launched): one launch writes
+ * one finished record per final output.  A lane owns 4 consecutive outputs
+ * along the innermost dim and walks them through every row of every chunk
+ * layer in increasing index order with the previous w - 1 elements of each in
+ * registers, so every window sum is formed by the same additions as
+ * pyas_roll_axes followed by the combines form it: the records are equal byte
+ * for byte. */
+int pyas_roll_cols(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask,
+                   const pyas_roll_rule *rule, const pyas_grid *grid, pyas_roll *out,
+                   void *stream);
+/* pyas_spell_combine_segments / pyas_spell_combine_grid for roll records (same
+ * orders, same errors): the records of a segment must be listed, and the chunk
+ * layers must lie, in sequence order. */
+int pyas_roll_combine_segments(pyas_ctx *ctx, const pyas_roll *in, const int64_t *index,
+                               const int64_t *seg_offsets, int64_t n_segments,
+                               pyas_roll *out, void *stream);
+int pyas_roll_combine_grid(pyas_ctx *ctx, const pyas_roll *in, const pyas_grid *grid,
+                           pyas_roll *out, void *stream);
+/* value[i] = best (stat PYAS_ROLL_SUM) or best / float64(window)
+ * (PYAS_ROLL_MEAN) of record i, masked[i] = (n_windows == 0), all device: 9
+ * bytes per output cross PCIe instead of 144.  A masked value is 0. */
+int pyas_roll_finalize(pyas_ctx *ctx, const pyas_roll *in, int64_t n, int32_t stat,
+                       double *value, uint8_t *masked, void *stream);
+
 /* ---- per-label second moments (Active.grouped) -------------------------------
  * The pyas_moments record, one per (output, group): an element whose global
  * index along one reduced dim is i belongs to group labels[i] >= 0, or to no

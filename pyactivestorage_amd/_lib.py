@@ -84,6 +84,28 @@ SPELL_OPS = {"gt": 0, "ge": 1, "lt": 2, "le": 3}              # PYAS_SPELL_GT ..
 SPELL_STATS = {"longest": 0, "days": 1, "events": 2}          # PYAS_SPELL_LONGEST .. PYAS_SPELL_EVENTS
 
 
+ROLL_MAX_WINDOW = 8   # pyas.h PYAS_ROLL_MAX_WINDOW
+
+
+class Roll(ctypes.Structure):
+    """pyas_roll: the extreme window sum of a sequence and its first and last window - 1 elements (merged in
+    sequence order only)."""
+    _fields_ = [("best", ctypes.c_double), ("position", ctypes.c_int32), ("n_windows", ctypes.c_int32),
+                ("n", ctypes.c_int32), ("len", ctypes.c_int32), ("window", ctypes.c_uint8),
+                ("which", ctypes.c_uint8), ("head_ok", ctypes.c_uint8), ("tail_ok", ctypes.c_uint8),
+                ("reserved", ctypes.c_int32), ("head", ctypes.c_double * (ROLL_MAX_WINDOW - 1)),
+                ("tail", ctypes.c_double * (ROLL_MAX_WINDOW - 1))]
+
+
+class RollRule(ctypes.Structure):
+    """pyas_roll_rule: the dim the windows follow, the window and max or min."""
+    _fields_ = [("dim", ctypes.c_int32), ("window", ctypes.c_int32), ("which", ctypes.c_int32)]
+
+
+ROLL_WHICH = {"max": 0, "min": 1}                             # PYAS_ROLL_MAX, PYAS_ROLL_MIN
+ROLL_STATS = {"sum": 0, "mean": 1}                            # PYAS_ROLL_SUM, PYAS_ROLL_MEAN
+
+
 class Argext(ctypes.Structure):
     """pyas_argext: the winning element of an arg-extreme (its value, its global index) and the unmasked count."""
     _fields_ = [("value", Scalar), ("index", ctypes.c_int32), ("n", ctypes.c_int32)]
@@ -265,6 +287,8 @@ WSUM_NBYTES = ctypes.sizeof(Wsum)
 assert WSUM_NBYTES == 32
 SPELL_NBYTES = ctypes.sizeof(Spell)
 assert SPELL_NBYTES == 40
+ROLL_NBYTES = ctypes.sizeof(Roll)
+assert ROLL_NBYTES == 144
 ARGEXT_NBYTES = ctypes.sizeof(Argext)
 assert ARGEXT_NBYTES == 16
 EXCEED_NBYTES = ctypes.sizeof(Exceed)
@@ -341,6 +365,13 @@ SIGNATURES = {
     "pyas_spell_combine_segments": [_vp, _vp, _vp, _vp, _i64, _vp, _vp],
     "pyas_spell_combine_grid": [_vp, _vp, ctypes.POINTER(Grid), _vp, _vp],
     "pyas_spell_finalize": [_vp, _vp, _i64, _i32, _vp, _vp, _vp],
+    "pyas_roll_axes": [_vp, ctypes.POINTER(Batch), ctypes.POINTER(Mask), ctypes.POINTER(RollRule), _u32, _vp, _vp,
+                       _vp],
+    "pyas_roll_cols": [_vp, ctypes.POINTER(Batch), ctypes.POINTER(Mask), ctypes.POINTER(RollRule),
+                       ctypes.POINTER(Grid), _vp, _vp],
+    "pyas_roll_combine_segments": [_vp, _vp, _vp, _vp, _i64, _vp, _vp],
+    "pyas_roll_combine_grid": [_vp, _vp, ctypes.POINTER(Grid), _vp, _vp],
+    "pyas_roll_finalize": [_vp, _vp, _i64, _i32, _vp, _vp, _vp],
     "pyas_argext_axes": [_vp, ctypes.POINTER(Batch), ctypes.POINTER(Mask), ctypes.POINTER(ArgextRule), _u32, _vp, _vp,
                          _vp],
     "pyas_argext_cols": [_vp, ctypes.POINTER(Batch), ctypes.POINTER(Mask), ctypes.POINTER(ArgextRule),

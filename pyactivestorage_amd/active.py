@@ -52,8 +52,8 @@ import warnings
 
 import numpy as np
 
-from . import _lib, argext, comoments, engine, exceed, grouped, histogram, moments, quantile, selection, spell, trend, \
-    weighted, zerosign
+from . import _lib, argext, comoments, engine, exceed, grouped, histogram, moments, quantile, rolling, selection, spell, \
+    trend, weighted, zerosign
 from .batch import ReductionPlan, _all_full
 from .device import DeviceBuffer, get_context
 from .dtypes import native, sum_dtype
@@ -430,6 +430,8 @@ class Active:
         self._grouped_path = None       # the last grouped query: "cols" (dense column kernel) or "walk"
         self._spell = None              # spell: {"along", "op", "threshold", "stat", "min_length"} of the next query
         self._spell_path = None         # the last spell query: "cols" (dense column kernel) or "walk"
+        self._rolling = None            # rolling: {"along", "window", "stat", "which"} of the next query
+        self._rolling_path = None       # the last rolling query: "cols" (dense column kernel) or "walk"
         self._argext = None             # argmax / argmin: {"along", "which", "name"} of the next query
         self._argext_path = None        # the last argmax / argmin query: "cols" (dense column kernel) or "walk"
         self._exceed = None             # exceed: {"op", "threshold", "stat"} of the next query
@@ -481,8 +483,17 @@ class Active:
         self._trend = None
         self._grouped = None
         self._spell = None
+        self._rolling = None
         self._argext = None
         self._exceed = None
+
+    @property
+    def rolling_path(self):
+        """Which kernel the last :meth:`rolling` query ran: ``"cols"`` (the
+        dense column walk, pyas_roll_cols) or ``"walk"`` (the per-element walk,
+        pyas_roll_axes); None before the first one and after a query that
+        reached no kernel (an empty selection)."""
+        return self._rolling_path
 
     @property
     def exceed_path(self):
@@ -705,6 +716,65 @@ class Active:
             raise ValueError(f"spell: {exc}") from None
         self._spell = settings
         self._method = "spell"
+        self._axis = (d,)
+        return self
+
+    def rolling(self, along, window, stat="sum", extreme="max"):
+        """The extreme running-window sum or mean along one dimension, per
+        output, in one pass on the device: Rx5day is
+        ``a.rolling(0, 5)[index]``, the hottest 3-day mean
+        ``a.rolling(0, 3, stat="mean")[index]``.  A *window* is ``window``
+        elements consecutive in the selection along ``along`` (with ``[::3]``,
+        every third element joins).  It is *valid* when all of its elements
+        are unmasked under ``_FillValue``, ``missing_value``, ``valid_min``
+        and ``valid_max``: a window with a missing day gives no value (a NaN
+        is data, not a missing day).  A valid window's sum is
+        ``s = f64(x[p]); s += f64(x[p+1]); ...; s += f64(x[p+w-1])``: every
+        element converts as ``astype(float64)`` does and the ``w - 1``
+        additions are float64, oldest element first.  This order is the
+        definition (no running add-and-subtract), so every path gives the
+        same bits.  The result is the largest (``extreme="max"``) or smallest
+        (``"min"``) valid window sum as float64; ``stat="mean"`` divides that
+        sum once by ``float64(window)`` (division by a positive constant is
+        monotone, so this is the extreme of the means).  A NaN sum (a NaN
+        element, or ``+inf`` and ``-inf`` in one window) propagates as in
+        ``np.max`` / ``np.min``: the first window whose sum is NaN wins.
+        Among equal sums the first window wins; ``-0.0 == +0.0``.  ``along``:
+        an int in ``[-ndim, ndim)``, the only reduced axis, kept with extent
+        1; ``window``: an int in ``1 .. 8`` (NotImplementedError beyond,
+        ValueError for anything that is not an int >= 1).  The result is
+        masked where an output has no valid window: fewer than ``window``
+        selected positions, or a masked element in every window.  With
+        ``components`` a dict of ``value`` (the result), ``sum`` (the extreme
+        window sum), ``position`` (int64, the position in the selection of
+        the winning window's first element, masked like ``value``),
+        ``n_windows`` (valid windows), ``n`` (unmasked positions), ``len``
+        (positions) and the record's other fields (``best``, ``window``,
+        ``which``, ``head``, ``tail``, ``head_ok``, ``tail_ok``: see
+        :mod:`.rolling`), so ``rolling.merge`` joins the components of
+        selections that follow each other along ``along`` (years, files)
+        with the windows across the join, and ``rolling.finalize`` reads the
+        result.  The selection along ``along`` must be a slice of step >= 1,
+        a strictly increasing index list or a boolean mask (ValueError
+        otherwise) of fewer than 2^31 positions.  A unit-step box query with
+        ``along=0`` and a dimension behind it runs the dense column kernel
+        (pyas_roll_cols), anything else the per-element walk
+        (pyas_roll_axes): see :attr:`rolling_path`; both give the same
+        records byte for byte.  The settings hold for one query."""
+        ndim = self.ds.ndim
+        if isinstance(along, (bool, np.bool_)) or not isinstance(along, (int, np.integer)) \
+                or not -ndim <= along < ndim:
+            raise ValueError(f"rolling: along={along!r} is out of range for {ndim} dimensions")
+        d = int(along) % ndim
+        try:
+            settings = {"along": d, "window": rolling.check_window(window), "stat": rolling.check_stat(stat),
+                        "which": rolling.check_extreme(extreme)}
+        except ValueError as exc:
+            raise ValueError(f"rolling: {exc}") from None
+        except NotImplementedError as exc:
+            raise NotImplementedError(f"rolling: {exc}") from None
+        self._rolling = settings
+        self._method = "rolling"
         self._axis = (d,)
         return self
 
@@ -962,6 +1032,7 @@ class Active:
             self._trend = None           # and a trend's coordinate
             self._grouped = None         # and a grouped query's labels
             self._spell = None           # and a spell's threshold
+            self._rolling = None         # and a rolling query's window
             self._argext = None          # and an arg-extreme's dimension
             self._exceed = None          # and an exceed query's threshold
             for store in held:
@@ -996,6 +1067,9 @@ class Active:
         sp = self._method == "spell"
         if sp and self.group is not None:
             raise NotImplementedError("spell with group=…: spell records are reduced on one GPU only")
+        ro = self._method == "rolling"
+        if ro and self.group is not None:
+            raise NotImplementedError("rolling with group=…: running-window records are reduced on one GPU only")
         ax = self._method in ("argmax", "argmin")
         if ax and self.group is not None:
             raise NotImplementedError(f"{self._method} with group=…: arg-extreme records are reduced on one GPU only")
@@ -1013,10 +1087,11 @@ class Active:
             raise ValueError(f"grouped: along={self._grouped['along']} is not among the reduced axes "
                              f"{self._norm_axes()}: every output would hold one label")
         cache_key = None
-        # (var / std, weighted, histogram, quantile, cov / corr, trend, grouped, spell, arg-extreme and exceed queries
-        # bypass the plan cache: its plans replay pyas_partial launches)
+        # (var / std, weighted, histogram, quantile, cov / corr, trend, grouped, spell, rolling, arg-extreme and exceed
+        # queries bypass the plan cache: its plans replay pyas_partial launches)
         if self.resident and self.group is None and self._method is not None and not second and not has_w \
-                and not hist and not quant and not co and not tr and not gr and not sp and not ax and not ex:
+                and not hist and not quant and not co and not tr and not gr and not sp and not ro and not ax \
+                and not ex:
             ikey = _index_key(index)
             if ikey is not None:
                 cache_key = (ikey, self._norm_axes(), _missing_key(self.missing))
@@ -1027,6 +1102,10 @@ class Active:
             decode_filters(ds.filter_pipeline, ds.dtype.itemsize, ds.name)
         if sp:
             self._check_spell_index(index)
+        if ro:
+            self._check_ordered_index(index, self._rolling["along"], "rolling",
+                                      "windows follow the selection in increasing order",
+                                      "windows follow the selection in order")
         if ax:
             self._check_ordered_index(index, self._argext["along"], self._method,
                                       "positions follow the selection in increasing order",
@@ -1056,6 +1135,8 @@ class Active:
             return self._reduce_grouped(indexer, compressor, filters, self._norm_axes())
         if sp:
             return self._reduce_spell(indexer, compressor, filters)
+        if ro:
+            return self._reduce_rolling(indexer, compressor, filters)
         if ax:
             return self._reduce_argext(indexer, compressor, filters)
         if ex:
@@ -1769,6 +1850,77 @@ class Active:
             out["events_total"] = spell.finalize(parts, "events")
             return out
         return spell.finalize(parts, self._spell["stat"])
+
+    # -- rolling -----------------------------------------------------------------
+    def _reduce_rolling(self, indexer, compressor, filters):
+        """rolling: records of the window sums along the one reduced axis.  A
+        unit-step box query with ``along == 0`` and a dim behind it takes the
+        dense column kernel (pyas_roll_cols: one finished record per output,
+        the chunk layers walked in the kernel); anything else per-chunk
+        records (pyas_roll_axes) merged in the orders of
+        :meth:`_reduce_records`, each of which folds the chunks of an output
+        in increasing chunk order along the axis.  The value and its mask are
+        computed on the device (pyas_roll_finalize) unless ``components`` is
+        set."""
+        ds = self.ds
+        ro = self._rolling
+        along, axes = ro["along"], (ro["along"],)
+        self._rolling_path = None
+        if indexer.dim_indexers[along].nitems >= 2 ** 31:
+            raise NotImplementedError(f"rolling: {indexer.dim_indexers[along].nitems} selected positions along "
+                                      f"dimension {along}; the record counts in int32 (fewer than 2^31)")
+        q = self._query_plan(indexer, compressor, filters, axes)
+        final_shape, n_final = q.final_shape, q.n_final
+        if q.empty:
+            return self._format_rolling(np.zeros(final_shape, dtype=engine.roll_dtype))
+        ctx, st, plan = q.ctx, q.st, q.plan
+        rule = (along, ro["window"], ro["which"])
+        fin = DeviceBuffer(ctx, n_final * _lib.ROLL_NBYTES)
+
+        def launch(off_ptr, out_ptr):
+            engine.roll_axes(ctx, plan.batch, plan.mask_up.struct, *rule, off_ptr, out_ptr, st)
+        # the dense path: every dim one unit-step range, axis 0 reduced, a kept dim behind it
+        dense = q.dims is not None and axes == (0,) and ds.ndim > 1 and bool(np.all(q.table[:, :ds.ndim, 1] == 1))
+        done = False
+        if dense:
+            g = _grid_struct(ds.ndim, axes, final_shape, {"n_coords": [len(p) for p in q.dims]}, None, None)
+            done = engine.roll_cols(ctx, plan.batch, plan.mask_up.struct, *rule, g, fin.ptr, st)
+        keep = []
+        if not done:
+            fin, keep = self._reduce_records(q, axes, _lib.ROLL_NBYTES, launch, engine.roll_combine_segments,
+                                             engine.roll_combine_grid, fin=fin)
+        self._rolling_path = "cols" if done else "walk"
+        if self._components:
+            final = self._records_back(q, fin, keep, engine.roll_dtype)
+            del keep
+            return self._format_rolling(final)
+        # the value and its mask on the device: 9 bytes per output come back
+        vbuf = DeviceBuffer(ctx, n_final * 9)
+        engine.roll_finalize(ctx, fin.ptr, n_final, ro["stat"], vbuf.ptr, vbuf.ptr + 8 * n_final, st)
+        val = np.empty(n_final, dtype=np.float64)
+        msk = np.empty(n_final, dtype=np.uint8)
+        ctx.d2h(val, vbuf.ptr, st)
+        ctx.d2h(msk, vbuf.ptr + 8 * n_final, st)
+        ctx.synchronize(st)
+        del keep
+        return np.ma.MaskedArray(val.reshape(final_shape), mask=msk.reshape(final_shape).astype(bool))
+
+    def _format_rolling(self, parts):
+        """The float64 result of a rolling query from its combined records on
+        the host (rolling.finalize), or its components: the finalized value,
+        the winning window and the counts, and the record's fields."""
+        value = rolling.finalize(parts, self._rolling["stat"])
+        if not self._components:
+            return value
+        bad = np.ma.getmaskarray(value)
+        never = np.zeros(parts.shape, dtype=bool)
+        out = {name: np.ascontiguousarray(parts[name]) for name in rolling.FIELDS}
+        out["value"] = value
+        out["sum"] = rolling.finalize(parts, "sum")
+        out["position"] = np.ma.MaskedArray(parts["position"].astype(np.int64), mask=bad)
+        for name in ("n_windows", "n", "len"):
+            out[name] = np.ma.MaskedArray(parts[name].astype(np.int64), mask=never)
+        return out
 
     # -- argmax / argmin ---------------------------------------------------------
     def _reduce_argext(self, indexer, compressor, filters):

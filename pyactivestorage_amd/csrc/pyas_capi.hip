@@ -1921,6 +1921,135 @@ int pyas_spell_finalize(pyas_ctx *ctx, const pyas_spell *in, int64_t n, int32_t 
     return PYAS_OK;
 }
 
+// pyas_roll_axes / pyas_roll_cols: the checks of the rule (check_spell's)
+static int check_roll(const pyas_roll_rule *rule, int ndim, uint32_t axes_mask) {
+    if (!rule) return fail(PYAS_EINVAL, "rule is NULL");
+    if (rule->dim < 0 || rule->dim >= ndim) return fail(PYAS_EINVAL, "rolling dim %d outside rank %d", rule->dim, ndim);
+    if (axes_mask != (1u << rule->dim))
+        return fail(PYAS_EINVAL, "axes mask 0x%x is not the rolling dim %d alone", axes_mask, rule->dim);
+    if (rule->window < 1 || rule->window > PYAS_ROLL_MAX_WINDOW)
+        return fail(PYAS_EINVAL, "window = %d outside 1..%d", rule->window, PYAS_ROLL_MAX_WINDOW);
+    if (rule->which != PYAS_ROLL_MAX && rule->which != PYAS_ROLL_MIN) return fail(PYAS_EINVAL, "which = %d", rule->which);
+    return PYAS_OK;
+}
+
+int pyas_roll_axes(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask, const pyas_roll_rule *rule,
+                   uint32_t axes_mask, const int64_t *out_offsets, pyas_roll *out, void *stream) {
+    if (!ctx) return fail(PYAS_EINVAL, "ctx is NULL");
+    if (batch && (batch->ndim < 1 || batch->ndim > PYAS_MAX_DIMS))
+        return fail(PYAS_ENOTSUP, "chunk rank %d outside 1..%d", batch->ndim, PYAS_MAX_DIMS);
+    pyas::RollArgs x;
+    std::memset(&x, 0, sizeof(x));
+    int es;
+    bool shuf, bsw, masked;
+    int rc = prepare(ctx, batch, mask, x.r, es, shuf, bsw, masked);
+    if (rc) return rc;
+    rc = check_roll(rule, batch->ndim, axes_mask);
+    if (rc) return rc;
+    const int64_t n = batch->n_chunks;
+    if (n == 0) return PYAS_OK;
+    if (!out) return fail(PYAS_EINVAL, "out is NULL");
+    if (batch->ndim > 1 && !out_offsets) return fail(PYAS_EINVAL, "out_offsets is NULL");
+    PYAS_HIP(hipSetDevice(ctx->device));
+    x.dim = rule->dim;
+    x.window = rule->window;
+    x.which = rule->which;
+    x.out_offsets = out_offsets;
+    x.out = out;
+    x.shuf = shuf;
+    x.bswap = bsw;
+    // a lane per kept output of the chunk, whichever dim the windows follow (1-D: one lane per chunk)
+    int64_t keep_elems = 1;
+    for (int d = 0; d < batch->ndim; ++d)
+        if (d != rule->dim) keep_elems *= batch->chunk_shape[d];
+    x.bpc = (keep_elems + pyas::kBlock - 1) / pyas::kBlock;
+    if (x.bpc > 64) x.bpc = 64;
+    if (x.bpc < 1) x.bpc = 1;
+    const int64_t grid = n * x.bpc;
+    if (grid >= (int64_t(1) << 31)) return fail(PYAS_ENOTSUP, "grid too large");
+    PYAS_HIP(pyas::launch_roll_axes(batch->dtype, x, grid, (hipStream_t)stream));
+    return PYAS_OK;
+}
+
+int pyas_roll_cols(pyas_ctx *ctx, const pyas_batch *batch, const pyas_mask *mask, const pyas_roll_rule *rule,
+                   const pyas_grid *g, pyas_roll *out, void *stream) {
+    if (!ctx) return fail(PYAS_EINVAL, "ctx is NULL");
+    if (!g) return fail(PYAS_EINVAL, "grid is NULL");
+    if (batch && (batch->ndim < 1 || batch->ndim > PYAS_MAX_DIMS))
+        return fail(PYAS_ENOTSUP, "chunk rank %d outside 1..%d", batch->ndim, PYAS_MAX_DIMS);
+    pyas::RollColsArgs x;
+    std::memset(&x, 0, sizeof(x));
+    int es;
+    bool shuf, bsw, masked;
+    int rc = prepare(ctx, batch, mask, x.r, es, shuf, bsw, masked);
+    if (rc) return rc;
+    const int nd = batch->ndim;
+    if (g->ndim != nd) return fail(PYAS_EINVAL, "grid rank %d, chunk rank %d", g->ndim, nd);
+    rc = check_roll(rule, nd, g->axes_mask);
+    if (rc) return rc;
+    int64_t n_layers = 1, n_cols = 1;
+    for (int d = 0; d < nd; ++d) {
+        if (g->n_coords[d] < 1) return fail(PYAS_EINVAL, "n_coords[%d] = %lld", d, (long long)g->n_coords[d]);
+        if ((g->axes_mask >> d) & 1u) {
+            n_layers *= g->n_coords[d];
+        } else {
+            if (g->out_extent[d] < 1) return fail(PYAS_EINVAL, "out_extent[%d] = %lld", d, (long long)g->out_extent[d]);
+            n_cols *= g->n_coords[d];
+        }
+    }
+    if (batch->n_chunks != n_layers * n_cols)
+        return fail(PYAS_EINVAL, "%lld chunks for a grid of %lld", (long long)batch->n_chunks,
+                    (long long)(n_layers * n_cols));
+    // the geometry the column walk takes: dim 0 reduced, at least one kept dim behind it
+    if (rule->dim != 0 || nd < 2) return fail(PYAS_ENOTSUP, "rolling dim %d of rank %d is not dim 0 before a kept dim", rule->dim, nd);
+    if (x.r.tab.on[0] || x.r.tab.on[1]) return fail(PYAS_ENOTSUP, "vector mask tables");
+    if (!out) return fail(PYAS_EINVAL, "out is NULL");
+    int64_t items = (batch->chunk_shape[nd - 1] + pyas::kTrendV - 1) / pyas::kTrendV;
+    for (int d = 1; d < nd - 1; ++d) items *= batch->chunk_shape[d];
+    const int64_t bpc = (items + pyas::kBlock - 1) / pyas::kBlock;
+    const int64_t grid = n_cols * bpc;
+    if (grid >= (int64_t(1) << 31)) return fail(PYAS_ENOTSUP, "grid of %lld workgroups", (long long)grid);
+    PYAS_HIP(hipSetDevice(ctx->device));
+    int64_t stride = 1;
+    for (int d = nd - 1; d >= 0; --d) {
+        x.n_coords[d] = g->n_coords[d];
+        x.ostride[d] = stride;
+        if (d >= 1) stride *= g->out_extent[d];
+    }
+    x.n_layers = n_layers;
+    x.n_cols = n_cols;
+    x.bpc = bpc;
+    x.out = out;
+    x.window = rule->window;
+    x.which = rule->which;
+    x.bswap = bsw;
+    x.masked = masked;
+    PYAS_HIP(pyas::launch_roll_cols(batch->dtype, x, shuf, grid, (hipStream_t)stream));
+    return PYAS_OK;
+}
+
+int pyas_roll_combine_segments(pyas_ctx *ctx, const pyas_roll *in, const int64_t *index, const int64_t *seg_offsets,
+                               int64_t n_segments, pyas_roll *out, void *stream) {
+    return combine_segments_records(ctx, in, index, seg_offsets, n_segments, out, stream,
+                                    pyas::launch_roll_segments);
+}
+
+int pyas_roll_combine_grid(pyas_ctx *ctx, const pyas_roll *in, const pyas_grid *g, pyas_roll *out, void *stream) {
+    return combine_grid_records(ctx, in, g, out, stream, pyas::launch_roll_grid);
+}
+
+int pyas_roll_finalize(pyas_ctx *ctx, const pyas_roll *in, int64_t n, int32_t stat, double *value, uint8_t *masked,
+                       void *stream) {
+    if (!ctx) return fail(PYAS_EINVAL, "ctx is NULL");
+    if (n < 0) return fail(PYAS_EINVAL, "negative record count");
+    if (stat != PYAS_ROLL_SUM && stat != PYAS_ROLL_MEAN) return fail(PYAS_EINVAL, "stat = %d", stat);
+    if (n == 0) return PYAS_OK;
+    if (!in || !value || !masked) return fail(PYAS_EINVAL, "NULL argument");
+    PYAS_HIP(hipSetDevice(ctx->device));
+    PYAS_HIP(pyas::launch_roll_finalize(in, n, stat, value, masked, (hipStream_t)stream));
+    return PYAS_OK;
+}
+
 // pyas_argext_axes / pyas_argext_cols: the checks of the rule
 static int check_argext(const pyas_argext_rule *rule, int ndim, uint32_t axes_mask) {
     if (!rule) return fail(PYAS_EINVAL, "rule is NULL");

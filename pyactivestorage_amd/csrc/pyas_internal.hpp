@@ -470,6 +470,34 @@ hipError_t launch_exceed_grid(const pyas_exceed *in, const pyas_grid &g, int64_t
                               pyas_exceed *out, hipStream_t st);
 hipError_t launch_exceed_finalize(const pyas_exceed *in, int64_t n, int32_t stat, const uint8_t *thr_masked,
                                   void *value, uint8_t *masked, hipStream_t st);
+// running-window extremes (pyas_rolling.hip): pyas_roll records, merged in sequence order
+struct RollArgs {
+    ReduceArgs r;                     // r.out unused
+    int32_t dim;                      // the one reduced dim
+    int32_t window, which;
+    int64_t bpc;                      // workgroups per chunk
+    const int64_t *out_offsets;       // NULL (1-D variables only): chunk c's record at out[c]
+    pyas_roll *out;
+    bool shuf, bswap;
+};
+struct RollColsArgs {
+    ReduceArgs r;                     // r.out unused; r.sel NULL: whole chunks
+    int64_t n_coords[PYAS_MAX_DIMS];  // chunk coordinates per dim (chunk n = C-order position)
+    int64_t ostride[PYAS_MAX_DIMS];   // final-output element strides (kept dims)
+    int64_t n_layers, n_cols;         // chunks along dim 0 / the kept dims
+    int64_t bpc;                      // workgroups per column
+    pyas_roll *out;                   // one finished record per final output
+    int32_t window, which;
+    bool bswap, masked;
+};
+hipError_t launch_roll_axes(int dtype, const RollArgs &a, int64_t grid, hipStream_t st);
+hipError_t launch_roll_cols(int dtype, const RollColsArgs &a, bool shuf, int64_t grid, hipStream_t st);
+hipError_t launch_roll_segments(const pyas_roll *in, const int64_t *index, const int64_t *seg, int64_t n_seg,
+                                pyas_roll *out, hipStream_t st);
+hipError_t launch_roll_grid(const pyas_roll *in, const pyas_grid &g, int64_t n_out, int64_t n_layers,
+                            pyas_roll *out, hipStream_t st);
+hipError_t launch_roll_finalize(const pyas_roll *in, int64_t n, int32_t stat, double *value, uint8_t *masked,
+                                hipStream_t st);
 // per-label second moments (pyas_grouped.hip): pyas_moments records, one per (output, group)
 constexpr int kGroupV = 4;            // k_group_cols: consecutive outputs per lane
 constexpr int kGroupRows = PYAS_GROUP_ROWS;   // k_group_cols: rows of the sorted list staged in LDS per pass (16 KiB)

@@ -24,13 +24,13 @@ __global__ __launch_bounds__(kBlock) void k_rec_tiles(const R *tiles, int64_t tp
     out[out_offsets ? out_offsets[c] : c] = p;
 }
 
-template <typename R, typename M>
+// U records in flight, merged in index order (fewer for a large record)
+template <typename R, typename M, int U = 8>
 __global__ __launch_bounds__(kBlock) void k_rec_segments(const R *in, const int64_t *index, const int64_t *seg,
                                                          int64_t n_seg, R *out) {
     const int64_t sidx = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (sidx >= n_seg) return;
     R p{};
-    constexpr int U = 8;   // U records in flight, merged in index order
     const int64_t k1 = seg[sidx + 1];
     for (int64_t k0 = seg[sidx]; k0 < k1; k0 += U) {
         R q[U];
@@ -102,11 +102,11 @@ hipError_t launch_rec_tiles(const R *tiles, int64_t tpc, int64_t n_chunks, const
     return hipGetLastError();
 }
 
-template <typename R, typename M>
+template <typename R, typename M, int U = 8>
 hipError_t launch_rec_segments(const R *in, const int64_t *index, const int64_t *seg, int64_t n_seg, R *out,
                                hipStream_t st) {
     const int64_t nb = (n_seg + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL((k_rec_segments<R, M>), dim3((unsigned)nb), dim3(kBlock), 0, st, in, index, seg, n_seg, out);
+    hipLaunchKernelGGL((k_rec_segments<R, M, U>), dim3((unsigned)nb), dim3(kBlock), 0, st, in, index, seg, n_seg, out);
     return hipGetLastError();
 }
 

@@ -35,6 +35,11 @@ comoments_dtype = np.dtype([("count", "<i8"), ("mean_x", "<f8"), ("mean_y", "<f8
 spell_dtype = np.dtype([(name, "<i4") for name in ("n", "n_true", "len", "head", "tail", "best", "days", "events",
                                                    "min_length", "reserved")])
 
+# Host view of ``pyas_roll``
+roll_dtype = np.dtype([("best", "<f8"), ("position", "<i4"), ("n_windows", "<i4"), ("n", "<i4"), ("len", "<i4"),
+                       ("window", "u1"), ("which", "u1"), ("head_ok", "u1"), ("tail_ok", "u1"), ("reserved", "<i4"),
+                       ("head", "<f8", (_lib.ROLL_MAX_WINDOW - 1,)), ("tail", "<f8", (_lib.ROLL_MAX_WINDOW - 1,))])
+
 # Host view of ``pyas_argext``; ``value`` holds the bits of the pyas_scalar (view it as f8 / i8 / u8 by the
 # data's class: :func:`pyactivestorage_amd.argext.values`)
 argext_dtype = np.dtype([("value", "<u8"), ("index", "<i4"), ("n", "<i4")])
@@ -348,6 +353,52 @@ def spell_finalize(ctx: Context, in_ptr, n: int, stat: str, value_ptr, mask_ptr,
     ``n`` records as int32 values and mask bytes, on the device."""
     _lib.check(ctx.lib.pyas_spell_finalize(ctx.handle, in_ptr, int(n), _lib.SPELL_STATS[stat], value_ptr, mask_ptr,
                                            stream), "pyas_spell_finalize")
+
+
+def _roll_rule(dim: int, window: int, which: str) -> _lib.RollRule:
+    return _lib.RollRule(int(dim), int(window), _lib.ROLL_WHICH[which])
+
+
+def roll_axes(ctx: Context, batch: _lib.Batch, mask: _lib.Mask, dim: int, window: int, which: str,
+              out_offsets_ptr, out_ptr, stream) -> None:
+    """pyas_roll_axes: running-window records along chunk dim ``dim`` (the one
+    reduced dim); ``out_offsets_ptr`` None for a 1-D variable."""
+    rule = _roll_rule(dim, window, which)
+    _lib.check(ctx.lib.pyas_roll_axes(ctx.handle, ctypes.byref(batch), ctypes.byref(mask), ctypes.byref(rule),
+                                      1 << int(dim), out_offsets_ptr, out_ptr, stream), "pyas_roll_axes")
+
+
+def roll_cols(ctx: Context, batch: _lib.Batch, mask: _lib.Mask, dim: int, window: int, which: str,
+              grid: _lib.Grid, out_ptr, stream) -> bool:
+    """pyas_roll_cols: one finished record per final output of a unit-step
+    box query with dim 0 the one reduced dim.  False when the geometry is
+    not the dense path's (PYAS_ENOTSUP): the caller runs :func:`roll_axes`."""
+    rule = _roll_rule(dim, window, which)
+    rc = ctx.lib.pyas_roll_cols(ctx.handle, ctypes.byref(batch), ctypes.byref(mask), ctypes.byref(rule),
+                                ctypes.byref(grid), out_ptr, stream)
+    if rc == _lib.ENOTSUP:
+        return False
+    _lib.check(rc, "pyas_roll_cols")
+    return True
+
+
+def roll_combine_segments(ctx: Context, in_ptr, index_ptr, seg_ptr, n_seg, out_ptr, stream) -> None:
+    """pyas_roll_combine_segments (``index_ptr`` None: the identity); the
+    records of a segment are listed in sequence order."""
+    _lib.check(ctx.lib.pyas_roll_combine_segments(ctx.handle, in_ptr, index_ptr, seg_ptr, int(n_seg), out_ptr,
+                                                  stream), "pyas_roll_combine_segments")
+
+
+def roll_combine_grid(ctx: Context, in_ptr, grid: _lib.Grid, out_ptr, stream) -> None:
+    _lib.check(ctx.lib.pyas_roll_combine_grid(ctx.handle, in_ptr, ctypes.byref(grid), out_ptr, stream),
+               "pyas_roll_combine_grid")
+
+
+def roll_finalize(ctx: Context, in_ptr, n: int, stat: str, value_ptr, mask_ptr, stream) -> None:
+    """pyas_roll_finalize: ``stat`` (``sum`` or ``mean``) of ``n`` records as
+    float64 and the mask bytes, on the device."""
+    _lib.check(ctx.lib.pyas_roll_finalize(ctx.handle, in_ptr, int(n), _lib.ROLL_STATS[stat], value_ptr, mask_ptr,
+                                          stream), "pyas_roll_finalize")
 
 
 def _argext_rule(dim: int, which: str, origin_ptr) -> _lib.ArgextRule:
