@@ -1106,6 +1106,54 @@ int pyas_wsum_combine_segments(pyas_ctx *ctx, const pyas_wsum *in, const int64_t
 int pyas_wsum_combine_grid(pyas_ctx *ctx, const pyas_wsum *in, const pyas_grid *grid,
                            pyas_wsum *out, void *stream);
 
+/* ---- weighted second moments (Active.var / std / cov / corr with weights=) ----
+ * Partial record of a weighted covariance over a set of pairs (64 bytes):
+ * count pairs unmasked on both sides; sw = sum w and sw2 = sum w^2 over them;
+ * mean_x = sum w x / sw and mean_y; m2_x = sum w (x - mean_x)^2, m2_y likewise
+ * and cxy = sum w (x - mean_x)(y - mean_y)  (all in f64; the weights as for
+ * pyas_wsum, values converted as astype(float64) does).  The all-zero record is
+ * neutral.  One pass: each lane keeps shifts Kx, Ky (its first counted pair of
+ * weight > 0; 0 before it, where every term has weight exactly 0) with
+ * sum w (x-Kx), sum w (x-Kx)^2, sum w (y-Ky), sum w (y-Ky)^2 and
+ * sum w (x-Kx)(y-Ky) in f64 (FMA), and finishes to mean = K + s1/sw,
+ * m2 = s2 - s1^2/sw (sw == 0: mean 0, m2 = s2).  Lanes, waves, tiles and chunks
+ * merge a then b in the fixed order of the moments records: count, sw and sw2
+ * add; when both sw > 0,
+ *   d_x = mean_x_b - mean_x_a;  f = sw_b / (sw_a + sw_b);
+ *   mean_x = mean_x_a + d_x f;  m2_x = m2_x_a + m2_x_b + d_x d_x sw_a f;
+ *   cxy = cxy_a + cxy_b + d_x d_y sw_a f
+ * (y likewise); a side with sw == 0 gives no mean, but its m2_x, m2_y and cxy
+ * (each exactly 0, or NaN) are still added, so results are bit-identical from
+ * run to run.  The m2s are clamped at 0, cxy is not.  A counted NaN or +-inf on
+ * either side gives a NaN cxy (and a NaN m2 on that side) at any weight,
+ * exactly 0 included; masked elements are excluded by select and never reach a
+ * product. */
+typedef struct {
+    int64_t count;
+    double sw, sw2, mean_x, mean_y, m2_x, m2_y, cxy;
+} pyas_wcomoments;
+
+/* pyas_comoments_axes with weights.  y == NULL (mask_y ignored): one variable;
+ * mean_y, m2_y and cxy are written 0 and no second buffer is read.  Otherwise x
+ * and y must agree as for pyas_comoments_axes (PYAS_EINVAL; dtypes
+ * PYAS_ENOTSUP) and the selection of both sides is x's.  PYAS_EINVAL when
+ * weights or one of its pointers is NULL.  Outputs, out_offsets and the other
+ * errors as pyas_moments_axes.  With every dim in axes_mask a selection that is
+ * one contiguous run streams 16-byte loads when the two sides agree in shuffle
+ * and their chunk bases are misaligned alike (base & 15), and is walked per
+ * element otherwise. */
+int pyas_wcomoments_axes(pyas_ctx *ctx, const pyas_batch *x, const pyas_mask *mask_x,
+                         const pyas_batch *y, const pyas_mask *mask_y, const pyas_weights *weights,
+                         uint32_t axes_mask, const int64_t *out_offsets, pyas_wcomoments *out,
+                         void *stream);
+/* pyas_moments_combine_segments / pyas_moments_combine_grid for wcomoments
+ * records (same orders, same errors). */
+int pyas_wcomoments_combine_segments(pyas_ctx *ctx, const pyas_wcomoments *in, const int64_t *index,
+                                     const int64_t *seg_offsets, int64_t n_segments,
+                                     pyas_wcomoments *out, void *stream);
+int pyas_wcomoments_combine_grid(pyas_ctx *ctx, const pyas_wcomoments *in, const pyas_grid *grid,
+                                 pyas_wcomoments *out, void *stream);
+
 /* ---- binned counts (Active.histogram) -----------------------------------------
  * Bin rule, over n_bins + 1 strictly increasing finite f64 edges e: an
  * unmasked selected element x (converted to f64 as astype(float64) does)

@@ -55,6 +55,13 @@ class Wsum(ctypes.Structure):
                 ("reserved", ctypes.c_uint64)]
 
 
+class Wcomoments(ctypes.Structure):
+    """pyas_wcomoments: count, sum w, sum w^2, weighted means, m2s and cxy of a set of pairs."""
+    _fields_ = [("count", ctypes.c_int64), ("sw", ctypes.c_double), ("sw2", ctypes.c_double),
+                ("mean_x", ctypes.c_double), ("mean_y", ctypes.c_double), ("m2_x", ctypes.c_double),
+                ("m2_y", ctypes.c_double), ("cxy", ctypes.c_double)]
+
+
 class Weights(ctypes.Structure):
     """pyas_weights: the per-dim factor vectors and each chunk's origin in them (device pointers)."""
     _fields_ = [("pool", ctypes.c_void_p), ("origin", ctypes.c_void_p)]
@@ -285,6 +292,8 @@ COMOMENTS_NBYTES = ctypes.sizeof(Comoments)
 assert COMOMENTS_NBYTES == 48
 WSUM_NBYTES = ctypes.sizeof(Wsum)
 assert WSUM_NBYTES == 32
+WCOMOMENTS_NBYTES = ctypes.sizeof(Wcomoments)
+assert WCOMOMENTS_NBYTES == 64
 SPELL_NBYTES = ctypes.sizeof(Spell)
 assert SPELL_NBYTES == 40
 ROLL_NBYTES = ctypes.sizeof(Roll)
@@ -398,6 +407,10 @@ SIGNATURES = {
                        _vp],
     "pyas_wsum_combine_segments": [_vp, _vp, _vp, _vp, _i64, _vp, _vp],
     "pyas_wsum_combine_grid": [_vp, _vp, ctypes.POINTER(Grid), _vp, _vp],
+    "pyas_wcomoments_axes": [_vp, ctypes.POINTER(Batch), ctypes.POINTER(Mask), ctypes.POINTER(Batch),
+                             ctypes.POINTER(Mask), ctypes.POINTER(Weights), _u32, _vp, _vp, _vp],
+    "pyas_wcomoments_combine_segments": [_vp, _vp, _vp, _vp, _i64, _vp, _vp],
+    "pyas_wcomoments_combine_grid": [_vp, _vp, ctypes.POINTER(Grid), _vp, _vp],
     "pyas_hist_axes": [_vp, ctypes.POINTER(Batch), ctypes.POINTER(Mask), ctypes.POINTER(Hist), _u32, _vp, _vp, _vp,
                        _vp],
     "pyas_hist_reset": [_vp, _vp, _i64, _i32, _vp],

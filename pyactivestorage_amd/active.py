@@ -53,7 +53,7 @@ import warnings
 import numpy as np
 
 from . import _lib, argext, comoments, engine, exceed, grouped, histogram, moments, quantile, rolling, selection, spell, \
-    trend, weighted, zerosign
+    trend, weighted, wmoments, zerosign
 from .batch import ReductionPlan, _all_full
 from .device import DeviceBuffer, get_context
 from .dtypes import native, sum_dtype
@@ -421,6 +421,7 @@ class Active:
         self._method = None
         self._ddof = 0                  # var / std: the divisor is count - ddof
         self._weights = None            # mean / sum: {dim: float64 vector} of the next query
+        self._mweights = None           # var / std / cov / corr: the weights= keyword of the next query
         self._hist = None               # histogram: the bins of the next query (_check_hist)
         self._quant = None              # quantile: {"q": float64 (0-D or 1-D), "method": str} of the next query
         self._co = None                 # cov / corr: the second variable's Active of the next query
@@ -477,6 +478,7 @@ class Active:
         self._method = value
         self._ddof = 0
         self._weights = None
+        self._mweights = None
         self._hist = None
         self._quant = None
         self._co = None
@@ -538,7 +540,10 @@ class Active:
 
     @property
     def weights(self):
-        """The weights of the next query (``{dim: float64 vector}``) or None."""
+        """The weights of the next :meth:`mean` / :meth:`sum` query (``{dim:
+        float64 vector}``) or None.  The property belongs to those two: a
+        :meth:`var`, :meth:`std`, :meth:`cov` or :meth:`corr` query takes its
+        weights through its own ``weights=`` keyword and refuses the property."""
         return self._weights
 
     @weights.setter
@@ -611,17 +616,30 @@ class Active:
             self._axis = axis
         return self
 
-    def var(self, axis=None, ddof=0):
+    def var(self, axis=None, ddof=0, weights=None):
         """Variance of the unmasked elements, ``m2 / (count - ddof)`` in
         float64 (``np.ma.var`` of the float64 selection), masked where
-        ``count - ddof <= 0``.  One pass on the device (pyas_moments_axes)."""
-        return self._set_moments("var", axis, ddof)
+        ``count - ddof <= 0``.  One pass on the device (pyas_moments_axes).
 
-    def std(self, axis=None, ddof=0):
+        With ``weights = {dim: vector}`` (the mapping :meth:`mean` takes; the
+        ``weights`` property belongs to :meth:`mean` / :meth:`sum` and is
+        refused here) the weighted variance ``m2 / fact`` in float64:
+        ``m2 = sum w (x - mean)^2`` about the weighted mean, and
+        ``fact = (sw sw - ddof sw2) / sw`` with ``sw = sum w``,
+        ``sw2 = sum w^2``, the normaliser of ``np.cov(aweights=w, ddof=ddof)``.
+        Masked where ``sw == 0`` or ``sw sw - ddof sw2 <= 0``; a counted NaN or
+        infinity gives NaN at any weight, exactly 0 included.  One pass on the
+        device (pyas_wcomoments_axes).  With ``components`` the result is a
+        dict of ``mean``, ``m2``, ``n``, ``sum_of_weights`` and
+        ``sum_of_weights2``; ``wmoments.merge`` combines the records of
+        disjoint selections.  The keyword holds for one query."""
+        return self._set_moments("var", axis, ddof, weights)
+
+    def std(self, axis=None, ddof=0, weights=None):
         """Standard deviation: the square root of :meth:`var`."""
-        return self._set_moments("std", axis, ddof)
+        return self._set_moments("std", axis, ddof, weights)
 
-    def cov(self, other, axis=None, ddof=0):
+    def cov(self, other, axis=None, ddof=0, weights=None):
         """Covariance with ``other``, an ``Active`` over a second variable of
         the same shape, chunks and dtype (byte order and filters may differ;
         it may be this object): ``cxy / (n - ddof)`` in float64 over the pairs
@@ -635,15 +653,25 @@ class Active:
         ``cxy = sum (x - mean_x)(y - mean_y)``: the slope of the regression of
         ``other`` on this variable is ``cxy / m2_x``, and
         ``comoments.merge`` combines the components of disjoint selections.
-        The settings hold for one query."""
-        return self._set_comoments("cov", other, axis, ddof)
+        The settings hold for one query.
 
-    def corr(self, other, axis=None):
+        With ``weights`` (see :meth:`var`) the weighted covariance
+        ``cxy / fact`` with ``cxy = sum w (x - mean_x)(y - mean_y)`` about the
+        weighted means: ``np.cov(xs, ys, aweights=w, ddof=ddof)[0, 1]``,
+        masked as the weighted :meth:`var` (pyas_wcomoments_axes).  The
+        components then also hold ``sum_of_weights`` and
+        ``sum_of_weights2``."""
+        return self._set_comoments("cov", other, axis, ddof, weights)
+
+    def corr(self, other, axis=None, weights=None):
         """Pearson's correlation with ``other`` (see :meth:`cov`):
         ``cxy / sqrt(m2_x) / sqrt(m2_y)`` clipped to [-1, 1] as
         ``np.corrcoef`` clips.  Masked where no pair is counted; NaN, not
-        masked, where either variable is constant over the counted pairs."""
-        return self._set_comoments("corr", other, axis, 0)
+        masked, where either variable is constant over the counted pairs.
+        With ``weights`` (see :meth:`var`) the weighted centred correlation
+        (the pattern correlation of two fields under area weights), masked
+        where ``sum w == 0``."""
+        return self._set_comoments("corr", other, axis, 0, weights)
 
     def trend(self, along, coord=None, axis=None):
         """The least-squares slope of the data against a coordinate, per
@@ -990,16 +1018,18 @@ class Active:
         e = histogram.edges(bins)
         return {"n": e.size - 1, "edges": e, "uniform": False}
 
-    def _set_moments(self, method, axis, ddof):
+    def _set_moments(self, method, axis, ddof, weights=None):
         if isinstance(ddof, (bool, np.bool_)) or not isinstance(ddof, (int, np.integer)) or ddof < 0:
             raise ValueError(f"ddof must be a non-negative int. Got {ddof!r}")
+        mweights = self._check_weights(weights)
         self._method = method
         self._ddof = int(ddof)
+        self._mweights = mweights
         if axis is not None:
             self._axis = axis
         return self
 
-    def _set_comoments(self, method, other, axis, ddof):
+    def _set_comoments(self, method, other, axis, ddof, weights=None):
         if not isinstance(other, Active):
             raise TypeError(f"{method}: other must be an Active over the second variable. Got {other!r}")
         x, y = self.ds, other.ds
@@ -1012,7 +1042,7 @@ class Active:
                                       f"Got {x.dtype.str} and {y.dtype.str}")
         if other.device != self.device:
             raise ValueError(f"{method}: the two Active objects are on devices {self.device} and {other.device}")
-        self._set_moments(method, axis, ddof)
+        self._set_moments(method, axis, ddof, weights)
         self._co = other
         return self
 
@@ -1026,6 +1056,7 @@ class Active:
         finally:
             self._method = None          # active.py:633
             self._weights = None         # weights are per query
+            self._mweights = None        # and so is a second-moment query's weights= keyword
             self._hist = None            # and so are a histogram's bins
             self._quant = None           # and a quantile's q and method
             self._co = None              # and a cov / corr's second variable
@@ -1119,6 +1150,8 @@ class Active:
             if d.kind == "int":
                 raise IndexError("Can't do an active reduction when the index for "
                                  f"axis {i!r} drops the axis.")
+        if (second or co) and self._mweights is not None:
+            return self._reduce_wmoments(indexer, compressor, filters, self._norm_axes())
         if second:
             return self._reduce_moments(indexer, compressor, filters, self._norm_axes())
         if hist:
@@ -2427,18 +2460,20 @@ class Active:
         return out
 
     # -- weighted mean / sum ------------------------------------------------------
-    def _weight_tables(self, coords):
-        """pyas_weights of this query for the chunks at ``coords``: the pool (a
+    def _weight_tables(self, coords, weights=None):
+        """pyas_weights of this query (``weights``: of a second-moment query's
+        keyword) for the chunks at ``coords``: the pool (a
         run of 1.0 for the dims without weights, then each weighted dim's
         vector, zero-padded to whole chunks so that every factor of an edge
         chunk is readable) and each chunk's origin in it."""
         ds = self.ds
+        weights = self._weights if weights is None else weights
         coords = np.asarray(coords, dtype=np.int64).reshape(-1, ds.ndim)
         parts, pos = [np.ones(max(ds.chunks), dtype=np.float64)], max(ds.chunks)
         origin = np.zeros((len(coords), _lib.MAX_DIMS), dtype=np.int64)
-        for d in sorted(self._weights):
+        for d in sorted(weights):
             padded = np.zeros(-(-ds.shape[d] // ds.chunks[d]) * ds.chunks[d], dtype=np.float64)
-            padded[:ds.shape[d]] = self._weights[d]
+            padded[:ds.shape[d]] = weights[d]
             origin[:, d] = pos + coords[:, d] * ds.chunks[d]
             parts.append(padded)
             pos += padded.size
@@ -2464,6 +2499,48 @@ class Active:
         fin, keep = self._reduce_records(q, axes, _lib.WSUM_NBYTES, launch, engine.wsum_combine_segments,
                                          engine.wsum_combine_grid)
         return self._format_weighted(self._records_back(q, fin, keep, engine.wsum_dtype))
+
+    def _reduce_wmoments(self, indexer, compressor, filters, axes):
+        """var / std / cov / corr with weights=: per-chunk count / sw / sw2 /
+        means / m2s / cxy records (pyas_wcomoments_axes; cov / corr: one plan
+        per side, over the same chunk list and selections) merged with the
+        weighted Chan formula in the orders of :meth:`_reduce_records`."""
+        q = self._query_plan(indexer, compressor, filters, axes, pair=self._co)
+        if q.empty:
+            return self._format_wmoments(np.zeros(q.final_shape, dtype=engine.wcomoments_dtype))
+        ctx, st = q.ctx, q.st
+        wpool, worigin = self._weight_tables(q.coords, self._mweights)
+        wbuf = DeviceBuffer(ctx, wpool.nbytes + worigin.nbytes)
+        ctx.h2d(wbuf.ptr, wpool, st)
+        ctx.h2d(wbuf.ptr + wpool.nbytes, worigin, st)
+        by, my = (q.plan_y.batch, q.plan_y.mask_up.struct) if self._co is not None else (None, None)
+
+        def launch(off_ptr, out_ptr):
+            engine.wcomoments_axes(ctx, q.plan.batch, q.plan.mask_up.struct, by, my, wbuf.ptr,
+                                   wbuf.ptr + wpool.nbytes, q.axes_mask, off_ptr, out_ptr, st)
+        fin, keep = self._reduce_records(q, axes, _lib.WCOMOMENTS_NBYTES, launch, engine.wcomoments_combine_segments,
+                                         engine.wcomoments_combine_grid)
+        return self._format_wmoments(self._records_back(q, fin, keep, engine.wcomoments_dtype))
+
+    def _format_wmoments(self, parts):
+        """The float64 result of a weighted var / std / cov / corr query from
+        its combined records (wmoments.finalize_*), or its components."""
+        co = self._method in ("cov", "corr")
+        if self._components:
+            empty = parts["count"] == 0
+            names = {"mean_x": "mean_x", "mean_y": "mean_y", "m2_x": "m2_x", "m2_y": "m2_y", "cxy": "cxy"} if co \
+                else {"mean": "mean_x", "m2": "m2_x"}
+            names.update(sum_of_weights="sw", sum_of_weights2="sw2")
+            out = {name: np.ma.MaskedArray(np.ascontiguousarray(parts[field]), mask=empty)
+                   for name, field in names.items()}
+            out["n"] = np.ma.MaskedArray(np.ascontiguousarray(parts["count"]),
+                                         mask=np.zeros(parts.shape, dtype=bool))
+            return out
+        if self._method == "corr":
+            return wmoments.finalize_corr(parts)
+        if co:
+            return wmoments.finalize_cov(parts, self._ddof)
+        return wmoments.finalize_var(parts, self._ddof, std=self._method == "std")
 
     def _format_moments(self, parts):
         """The float64 result of a var / std query from its combined records

@@ -2529,6 +2529,82 @@ int pyas_wsum_combine_grid(pyas_ctx *ctx, const pyas_wsum *in, const pyas_grid *
     return combine_grid_records(ctx, in, g, out, stream, pyas::launch_wsum_grid);
 }
 
+int pyas_wcomoments_axes(pyas_ctx *ctx, const pyas_batch *bx, const pyas_mask *mask_x, const pyas_batch *by,
+                         const pyas_mask *mask_y, const pyas_weights *weights, uint32_t axes_mask,
+                         const int64_t *out_offsets, pyas_wcomoments *out, void *stream) {
+    if (!ctx) return fail(PYAS_EINVAL, "ctx is NULL");
+    if (!bx) return fail(PYAS_EINVAL, "batch is NULL");
+    if (bx->ndim < 1 || bx->ndim > PYAS_MAX_DIMS)
+        return fail(PYAS_ENOTSUP, "chunk rank %d outside 1..%d", bx->ndim, PYAS_MAX_DIMS);
+    // every check before any device call: the pairing first, then each side as pyas_moments_axes
+    if (by) {
+        if (by->ndim != bx->ndim) return fail(PYAS_EINVAL, "ranks differ: x %d, y %d", bx->ndim, by->ndim);
+        for (int d = 0; d < bx->ndim; ++d)
+            if (by->chunk_shape[d] != bx->chunk_shape[d])
+                return fail(PYAS_EINVAL, "chunk_shape[%d] differs: x %lld, y %lld", d,
+                            (long long)bx->chunk_shape[d], (long long)by->chunk_shape[d]);
+        if (by->n_chunks != bx->n_chunks)
+            return fail(PYAS_EINVAL, "n_chunks differs: x %lld, y %lld", (long long)bx->n_chunks,
+                        (long long)by->n_chunks);
+        if (by->dtype != bx->dtype) return fail(PYAS_ENOTSUP, "dtypes differ: x %d, y %d", bx->dtype, by->dtype);
+    }
+    pyas::WcomArgs x;
+    std::memset(&x, 0, sizeof(x));
+    int es, es_y;
+    bool shx, shy = false, bsx, bsy = false, mx, my = false;
+    int rc = prepare(ctx, bx, mask_x, x.x, es, shx, bsx, mx);
+    if (rc) return rc;
+    if (by) {
+        rc = prepare(ctx, by, mask_y, x.y, es_y, shy, bsy, my);
+        if (rc) return rc;
+    }
+    if (axes_mask >> bx->ndim) return fail(PYAS_EINVAL, "axes mask 0x%x beyond rank %d", axes_mask, bx->ndim);
+    const int64_t n = bx->n_chunks;
+    if (n == 0) return PYAS_OK;
+    if (!weights || !weights->pool || !weights->origin) return fail(PYAS_EINVAL, "weights is NULL or has a NULL table");
+    if (!out) return fail(PYAS_EINVAL, "out is NULL");
+    PYAS_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    x.axes = axes_mask;
+    x.out_offsets = out_offsets;
+    x.out = out;
+    x.wpool = weights->pool;
+    x.worigin = weights->origin;
+    x.bswap_x = bsx;
+    x.bswap_y = bsy;
+    x.masked_x = mx;
+    x.masked_y = my;
+    x.shuf_x = shx;
+    x.shuf_y = shy;
+    if (axes_mask == (1u << bx->ndim) - 1u) {
+        // every dim reduced: a workgroup per (chunk, tile) of one side's bytes; tiles merge in tile order
+        int64_t grid;
+        rc = full_geometry(ctx, stream, n, x.x.chunk_elems * es, x.bpc, grid, x.tiles);
+        if (rc) return rc;
+        PYAS_HIP(by ? pyas::launch_wcom2_full(bx->dtype, x, grid, st) : pyas::launch_wcom1_full(bx->dtype, x, grid, st));
+        if (x.bpc > 1) PYAS_HIP(pyas::launch_wcom_tiles(x.tiles, x.bpc, n, out_offsets, out, st));
+        return PYAS_OK;
+    }
+    if (!out_offsets) return fail(PYAS_EINVAL, "out_offsets is NULL");
+    axes_geometry(bx->ndim, bx->chunk_shape, axes_mask, x.row, x.bpc);
+    const int64_t grid = n * x.bpc;
+    if (grid >= (int64_t(1) << 31)) return fail(PYAS_ENOTSUP, "grid too large");
+    PYAS_HIP(by ? pyas::launch_wcom2_axes(bx->dtype, x, grid, st) : pyas::launch_wcom1_axes(bx->dtype, x, grid, st));
+    return PYAS_OK;
+}
+
+int pyas_wcomoments_combine_segments(pyas_ctx *ctx, const pyas_wcomoments *in, const int64_t *index,
+                                     const int64_t *seg_offsets, int64_t n_segments, pyas_wcomoments *out,
+                                     void *stream) {
+    return combine_segments_records(ctx, in, index, seg_offsets, n_segments, out, stream,
+                                    pyas::launch_wcom_segments);
+}
+
+int pyas_wcomoments_combine_grid(pyas_ctx *ctx, const pyas_wcomoments *in, const pyas_grid *g, pyas_wcomoments *out,
+                                 void *stream) {
+    return combine_grid_records(ctx, in, g, out, stream, pyas::launch_wcom_grid);
+}
+
 // The launch shapes shared by the counting kernels (binned counts and the
 // radix select's digit counts).
 // k_hist_full / k_qsel_full: log2 of the copies of an LDS table of `slots` slots (and a spare one)

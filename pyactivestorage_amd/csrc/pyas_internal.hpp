@@ -557,6 +557,31 @@ hipError_t launch_wsum_segments(const pyas_wsum *in, const int64_t *index, const
                                 pyas_wsum *out, hipStream_t st);
 hipError_t launch_wsum_grid(const pyas_wsum *in, const pyas_grid &g, int64_t n_out, int64_t n_layers,
                             pyas_wsum *out, hipStream_t st);
+// weighted second moments (pyas_wmoments.hip): count / sw / sw2 / means / m2s / cxy records
+struct WcomArgs {
+    ReduceArgs x;                     // x.out unused; the geometry and the selection of both sides
+    ReduceArgs y;                     // two variables: data, offsets, mask and tab only; else zero
+    uint32_t axes;                    // reduced dims
+    int64_t bpc;                      // workgroups per chunk (full: tiles per chunk)
+    const int64_t *out_offsets;       // NULL (full only): chunk c's record at out[c]
+    pyas_wcomoments *out;
+    pyas_wcomoments *tiles;           // full with bpc > 1: one record per workgroup
+    const double *wpool;              // pyas_weights
+    const int32_t *worigin;
+    bool bswap_x, bswap_y, masked_x, masked_y, shuf_x, shuf_y;
+    bool row;                         // innermost dim reduced: a wave per output
+};
+// wcom1: one variable (y unused); wcom2: two variables
+hipError_t launch_wcom1_full(int dtype, const WcomArgs &a, int64_t grid, hipStream_t st);
+hipError_t launch_wcom1_axes(int dtype, const WcomArgs &a, int64_t grid, hipStream_t st);
+hipError_t launch_wcom2_full(int dtype, const WcomArgs &a, int64_t grid, hipStream_t st);
+hipError_t launch_wcom2_axes(int dtype, const WcomArgs &a, int64_t grid, hipStream_t st);
+hipError_t launch_wcom_tiles(const pyas_wcomoments *tiles, int64_t tpc, int64_t n_chunks, const int64_t *out_offsets,
+                             pyas_wcomoments *out, hipStream_t st);
+hipError_t launch_wcom_segments(const pyas_wcomoments *in, const int64_t *index, const int64_t *seg, int64_t n_seg,
+                                pyas_wcomoments *out, hipStream_t st);
+hipError_t launch_wcom_grid(const pyas_wcomoments *in, const pyas_grid &g, int64_t n_out, int64_t n_layers,
+                            pyas_wcomoments *out, hipStream_t st);
 // binned counts (pyas_hist.hip): int64 table rows of n_bins + 3 slots
 constexpr int kHistLdsBins = 2048;    // most bins of the LDS form (k_hist_full) and of LDS-staged edges
 constexpr int kHistMaxCopies = 32;    // k_hist_full: most copies of its LDS table (one per lane of an LDS pass)

@@ -50,6 +50,10 @@ exceed_dtype = np.dtype([("n", "<i8"), ("n_true", "<i8"), ("sum", "<f8"), ("exce
 # Host view of ``pyas_wsum``
 wsum_dtype = np.dtype([("count", "<i8"), ("sw", "<f8"), ("swx", "<f8"), ("reserved", "<u8")])
 
+# Host view of ``pyas_wcomoments``
+wcomoments_dtype = np.dtype([("count", "<i8"), ("sw", "<f8"), ("sw2", "<f8"), ("mean_x", "<f8"), ("mean_y", "<f8"),
+                             ("m2_x", "<f8"), ("m2_y", "<f8"), ("cxy", "<f8")])
+
 
 @dataclass
 class Layout:
@@ -603,6 +607,30 @@ def wsum_combine_segments(ctx: Context, in_ptr, index_ptr, seg_ptr, n_seg, out_p
 def wsum_combine_grid(ctx: Context, in_ptr, grid: _lib.Grid, out_ptr, stream) -> None:
     _lib.check(ctx.lib.pyas_wsum_combine_grid(ctx.handle, in_ptr, ctypes.byref(grid), out_ptr, stream),
                "pyas_wsum_combine_grid")
+
+
+def wcomoments_axes(ctx: Context, batch_x: _lib.Batch, mask_x: _lib.Mask, batch_y, mask_y, pool_ptr, origin_ptr,
+                    axes_mask: int, out_offsets_ptr, out_ptr, stream) -> None:
+    """pyas_wcomoments_axes: count / sw / sw2 / means / m2s / cxy records per
+    chunk output, laid out like :func:`moments_axes`'; ``batch_y`` None: one
+    variable (``mask_y`` ignored); ``pool_ptr`` / ``origin_ptr``: pyas_weights."""
+    w = _lib.Weights(pool_ptr, origin_ptr)
+    by = ctypes.byref(batch_y) if batch_y is not None else None
+    my = ctypes.byref(mask_y) if batch_y is not None else None
+    _lib.check(ctx.lib.pyas_wcomoments_axes(ctx.handle, ctypes.byref(batch_x), ctypes.byref(mask_x), by, my,
+                                            ctypes.byref(w), int(axes_mask), out_offsets_ptr, out_ptr, stream),
+               "pyas_wcomoments_axes")
+
+
+def wcomoments_combine_segments(ctx: Context, in_ptr, index_ptr, seg_ptr, n_seg, out_ptr, stream) -> None:
+    """pyas_wcomoments_combine_segments (``index_ptr`` None: the identity)."""
+    _lib.check(ctx.lib.pyas_wcomoments_combine_segments(ctx.handle, in_ptr, index_ptr, seg_ptr, int(n_seg), out_ptr,
+                                                        stream), "pyas_wcomoments_combine_segments")
+
+
+def wcomoments_combine_grid(ctx: Context, in_ptr, grid: _lib.Grid, out_ptr, stream) -> None:
+    _lib.check(ctx.lib.pyas_wcomoments_combine_grid(ctx.handle, in_ptr, ctypes.byref(grid), out_ptr, stream),
+               "pyas_wcomoments_combine_grid")
 
 
 _FORMAT = {"sum": _lib.FORMAT_SUM, "min": _lib.FORMAT_MIN, "max": _lib.FORMAT_MAX,
